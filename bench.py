@@ -11,12 +11,19 @@ only the timing uses a barrier and a MAX all-reduce.
 
 ``value`` = algorithmic TFLOP/s of the whole job: ranks x 3*F_fwd per step /
 step time, F_fwd = B*H*T^2*(N*hs + dv) (causal-halved matmul FLOPs).
-``roofline`` reports the dominant kernel (the fused backward) from HIP events
-bracketing its launches inside the timed region.  ``cpu_baseline`` times the CPU
+
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) does only what that
+figure needs: it draws the inputs, warms up, times the N steps and prints the
+result line.  ``--dump-outputs DIR`` also writes what the last timed step
+returned (``dump_outputs`` below).  Everything else is behind ``--full``:
+
+``kernels`` / ``roofline`` report every kernel, and the dominant one (the fused
+backward), from HIP events bracketing its launches in a second pass of the same
+steps after the timed region.  ``cpu_baseline`` times the CPU
 oracle (the reference's algorithm op for op: per-head loop, materialised T x T
 maps, fp32) on a bounded sample on this host.
 
-The kernel line also carries:
+With ``--full`` the kernel line also carries:
   ``train``        BASELINE configs[3] -- the ~350M DiffTransformer DP training
                    step (bucketed RCCL all-reduce overlapped with backward) at
                    this run's world size: whole-job train tokens/s, so the 1/2/4/8
@@ -267,11 +274,33 @@ def _coefficients(H, N, hs, dev):
     return alternating_coefficients(lqs, lks, float(lambda_init_value(3, None)))
 
 
-def core_run(B, H, hs, N, T, steps, warmup, world=1, rank=0, dv=None):
+DUMP_SAMPLE = 1 << 21          # elements kept of each dumped array: 8 MiB as float32
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write every tensor of ``arrays`` as ``path/<name>.npy``, float32
+    (float64 stays float64).  An array of more than DUMP_SAMPLE elements is cut to a fixed
+    sample: its elements at DUMP_SAMPLE flat indices drawn from a CPU generator seeded with
+    0, in ascending order -- the same indices in every run and for every build, so two
+    dumps of one command compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t[idx.sort().values.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def core_run(B, H, hs, N, T, steps, warmup, world=1, rank=0, dv=None, kernel_times=True, dump=None):
     """Forward + backward of the fused attention core (bf16, causal, synthetic N(0,1)
     inputs resident in HBM) ``steps`` times after ``warmup``; the wall time of the
-    timed region (barrier + synchronize on both sides, MAX over ranks) and every
-    kernel's mean HIP-event time with its algorithmic TFLOP/s."""
+    timed region (barrier + synchronize on both sides, MAX over ranks) and, with
+    ``kernel_times``, every kernel's mean HIP-event time with its algorithmic TFLOP/s
+    (SURVEY 8d).  ``dump``: a folder for what the last timed step returned, the output
+    ``out`` and the gradient ``dqkv`` of the packed input (rank 0 writes)."""
     from differential_transformer_replication_amd import ops
     dv = 2 * hs if dv is None else dv
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -285,16 +314,26 @@ def core_run(B, H, hs, N, T, steps, warmup, world=1, rank=0, dv=None):
         qkv.grad = None
         out = ops.diff_attention(qkv, coef, H, N, hs, dv=dv)
         out.backward(do)
+        return out
 
     for _ in range(warmup):
         step()
     _sync(world)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    out = step()                   # the last timed step's output stays alive for --dump-outputs
     _sync(world)
     el = time.perf_counter() - t0
     el = _max_over_ranks(el, world)
+    if dump and rank == 0:
+        dump_outputs(dump, {"out": out, "dqkv": qkv.grad})
+    del out
+    f_fwd = float(B) * H * T * T * (N * hs + dv)
+    f_bwd = 2 * f_fwd
+    if not kernel_times:
+        del qkv, do
+        return el / steps, f_fwd + f_bwd, {}
     # per-kernel HIP-event times from a second pass of the same steps, after the timed region:
     # the six events per step add gaps between the launches (tools/host_overhead_probe.py: cfg3
     # N = 3 1.066 -> 1.151 ms per step with them, cfg2 2.880 -> 2.904), so they stay out of it
@@ -303,8 +342,6 @@ def core_run(B, H, hs, N, T, steps, warmup, world=1, rank=0, dv=None):
         step()
     ops.TIMER.stop()
     kt = ops.TIMER.mean_ms()
-    f_fwd = float(B) * H * T * T * (N * hs + dv)
-    f_bwd = 2 * f_fwd
     # per-kernel algorithmic FLOPs: the forward does F_fwd; the backward's 2*F_fwd is split by
     # its two kernels' products: dq (dQ = dS K) and dkdv (dV = P^T dO, dK = dS^T Q, dP = dO V^T)
     dq_share = N * hs / (2.0 * (N * hs + dv))
@@ -319,15 +356,10 @@ def core_run(B, H, hs, N, T, steps, warmup, world=1, rank=0, dv=None):
 def kernel_bench(args, world, rank):
     B, H, hs, N, T = args.batch, args.heads, args.head_size, args.n_terms, args.seq
     dv = 2 * hs
-    sec, flop, kernels = core_run(B, H, hs, N, T, args.steps, args.warmup, world, rank)
+    sec, flop, kernels = core_run(B, H, hs, N, T, args.steps, args.warmup, world, rank, kernel_times=args.full,
+                                  dump=args.dump_outputs)
     ms = sec * 1e3
     value = world * flop / sec / 1e12
-    dom = max(kernels, key=lambda k: kernels[k]["ms"])
-    achieved = kernels[dom]["alg_tflops"]
-    traffic, traffic_src = args.traffic, None
-    if traffic is None:
-        traffic, traffic_src = _pmc_traffic(dom, shape_key(B, H, hs, N, T, dv))
-    ghz, ghz_src = _sq_clock(dom, shape_key(B, H, hs, N, T, dv))
     cfg2 = (B, H, hs, N, T) == (8, 16, 64, 2, 4096)
     workload = ("cfg2: fused N=2 diff-attention core fwd+bwd (BASELINE configs[1])" if cfg2 else
                 f"diff-attention core fwd+bwd B={B} H={H} hs={hs} N={N} T={T}")
@@ -340,17 +372,24 @@ def kernel_bench(args, world, rank):
                    "seq_len": T, "n_terms": N, "causal": True,
                    "parallelism": f"batch-sharded replicas x{world} (no data-path collective)"},
         "mfma_frac_step": round(value / world / PEAK_BF16_TFLOPS, 4),
-        "kernels": kernels,
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     # the chip holds ~1.8-1.9 GHz under this load, not the 2.4 GHz the peak assumes:
-                     # the MFMA peak at the measured clock, and the fraction of it
-                     "clock_ghz": ghz, "clock_source": ghz_src,
-                     "peak_at_clock": round(PEAK_BF16_TFLOPS * ghz / 2.4, 1) if ghz else None,
-                     "frac_at_clock": round(achieved / (PEAK_BF16_TFLOPS * ghz / 2.4), 4) if ghz else None},
-        "lib_sha": lib_sha(),
     }
+    if args.full:
+        dom = max(kernels, key=lambda k: kernels[k]["ms"])
+        achieved = kernels[dom]["alg_tflops"]
+        traffic, traffic_src = args.traffic, None
+        if traffic is None:
+            traffic, traffic_src = _pmc_traffic(dom, shape_key(B, H, hs, N, T, dv))
+        ghz, ghz_src = _sq_clock(dom, shape_key(B, H, hs, N, T, dv))
+        res["kernels"] = kernels
+        res["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
+                           "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                           "traffic": traffic, "traffic_source": traffic_src,
+                           # the chip holds ~1.8-1.9 GHz under this load, not the 2.4 GHz the peak assumes:
+                           # the MFMA peak at the measured clock, and the fraction of it
+                           "clock_ghz": ghz, "clock_source": ghz_src,
+                           "peak_at_clock": round(PEAK_BF16_TFLOPS * ghz / 2.4, 1) if ghz else None,
+                           "frac_at_clock": round(achieved / (PEAK_BF16_TFLOPS * ghz / 2.4), 4) if ghz else None}
+    res["lib_sha"] = lib_sha()
     if args.control and rank == 0:
         # control.py standard attention at equal F_fwd: 2*H heads of width hs, dv = hs (train.py:226)
         Hc = 2 * H if N == 2 else H
@@ -428,10 +467,12 @@ def decode_bench(args, world, rank):
     t0 = time.perf_counter()
     for e0, e1 in ev:
         e0.record()
-        ops.diff_attention_decode(q, k, v, coef, L)
+        o = ops.diff_attention_decode(q, k, v, coef, L)
         e1.record()
     _sync(world)
     ms = _max_over_ranks((time.perf_counter() - t0) * 1e3 / args.steps, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": o})
     kms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     nbytes = B * H * L * (N * hs + dv) * 2
     return {"metric": "KV-cache decode attention GB/s (one new token per sequence)", "value": round(
@@ -580,16 +621,17 @@ def run(args):
         # the train leg first: run after the kernel and HBM legs in the same process it
         # measured 7-8% below a --mode train run on the same box
         train = None
-        if args.train_steps > 0 and os.environ.get("DTA_TRAIN_LEG_FIRST", "1") != "0":
+        train_steps = args.train_steps if args.full else 0          # every leg but the core: --full only
+        if train_steps > 0 and os.environ.get("DTA_TRAIN_LEG_FIRST", "1") != "0":
             train = train_leg(args, world, rank)
             torch.cuda.empty_cache()
         res = kernel_bench(args, world, rank)
-        if rank == 0 and args.hbm:
+        if args.full and rank == 0 and args.hbm:
             res["hbm_kernels"] = hbm_bench()
-        if world == 1 and args.configs and args.cfg_steps > 0:
+        if args.full and world == 1 and args.configs and args.cfg_steps > 0:
             torch.cuda.empty_cache()
             res["configs"] = configs_leg(args)
-        if args.train_steps > 0:
+        if train_steps > 0:
             if train is None:
                 torch.cuda.empty_cache()
                 train = train_leg(args, world, rank)
@@ -599,10 +641,13 @@ def run(args):
     else:
         from differential_transformer_replication_amd.train import train_bench
         res = train_bench(args, world, rank)
+        if args.dump_outputs and rank == 0:
+            # what the training loop hands back per step: the loss of the last timed one
+            dump_outputs(args.dump_outputs, {"final_loss": torch.tensor(res["final_loss"], dtype=torch.float64)})
     if rank == 0:
         default_kernel = args.mode == "kernel" and args.device == "cuda" and (
             args.batch, args.heads, args.head_size, args.n_terms, args.seq) == (8, 16, 64, 2, 4096)
-        if args.cpu_baseline == "auto" and world == 1 and default_kernel:
+        if args.full and args.cpu_baseline == "auto" and world == 1 and default_kernel:
             res["cpu_baseline"] = cpu_baseline()
         elif "cpu_baseline" not in res:
             res["cpu_baseline"] = None
@@ -633,6 +678,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=["kernel", "train", "decode"], default="kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="kernel mode: also the per-kernel HIP-event pass with the roofline, the cfg4 train leg, the "
+                         "LN / RoPE timings, the cfg3 / cfg5 legs and the CPU oracle baseline (the --train-steps, "
+                         "--no-hbm, --no-configs, --cfg-steps, --cpu-baseline and --traffic options act under it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of a large array): kernel mode out and dqkv, decode mode out, "
+                         "train mode final_loss")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: gloo dry run of the multi-rank path (train leg on a small control model)")
     ap.add_argument("--batch", type=int, default=8)
@@ -657,6 +710,8 @@ def main():
     ap.add_argument("--traffic", type=float, default=None,
                     help="HBM bytes per dominant-kernel launch from rocprofv3 PMC (profiles/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None and int(env_world) != args.gpus:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={env_world}", file=sys.stderr)

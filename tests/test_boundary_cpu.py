@@ -177,14 +177,23 @@ def test_seeded_init_matches_reference_diff_models(key):
 
 
 def test_seeded_init_matches_reference(golden_curve):
-    """Same seed -> bitwise the same initial weights as the reference cfg1 model."""
+    """Same seed -> the same initial weights as the reference cfg1 model, every parameter by its
+    float64 (sum, sum of squares).  The fixture's sums and these are float64 reductions whose
+    order follows the host's thread count and vector width, so each may be off its exact value
+    by a few rounding steps of the summed magnitudes (seen: 1 ulp on a 16-thread host, 2 of 414
+    sums).  The bar is 64 eps of sum|x| (of sum x^2): above twice a pairwise reduction's
+    log2(n) eps bound for the largest parameter (n = 4.6M, 22 eps), below what one float32
+    ulp of a typical weight changes."""
     torch.manual_seed(1337)
     m = D.DiffTransformer(12000, 384, 6, 6, 256, 0.0)
-    sums = np.array([float(p.detach().double().sum()) for p in m.parameters()])
-    sq = np.array([float(p.detach().double().pow(2).sum()) for p in m.parameters()])
+    ps = [p.detach().double() for p in m.parameters()]
+    sums = np.array([float(p.sum()) for p in ps])
+    sq = np.array([float(p.pow(2).sum()) for p in ps])
     assert sums.shape == golden_curve["curve/param_sum"].shape
-    np.testing.assert_array_equal(sums, golden_curve["curve/param_sum"])
-    np.testing.assert_array_equal(sq, golden_curve["curve/param_sq"])
+    eps = np.finfo(np.float64).eps
+    tol = 64 * eps * np.array([float(p.abs().sum()) for p in ps])
+    assert np.all(np.abs(sums - golden_curve["curve/param_sum"]) <= tol)
+    assert np.all(np.abs(sq - golden_curve["curve/param_sq"]) <= 64 * eps * sq)
 
 
 def test_control_cpu_matches_golden(golden):

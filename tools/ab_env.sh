@@ -7,6 +7,7 @@ timeout -k 10 300 python -u -m pytest tests/ -m gpu -q -x --timeout 120 --timeou
 tail -1 gpurun_out/tests.log
 fi
 for m in $VALS; do
-  env $VAR=$m timeout -k 10 120 python bench.py --cpu-baseline off ${BENCH_ARGS:-} > gpurun_out/ab_$m.json 2> gpurun_out/ab_$m.err || { echo "BENCH $m FAILED"; tail -5 gpurun_out/ab_$m.err; exit 1; }
-  python3 -c "import json,sys; d=json.load(open('gpurun_out/ab_$m.json')); print('$VAR=$m', d['ms_per_step'], {k: v['ms'] for k, v in d['kernels'].items()})"
+  O=${OUT_DIR:-bench_out}; mkdir -p $O
+  env $VAR=$m timeout -k 10 120 python bench.py --full --cpu-baseline off ${BENCH_ARGS:-} > $O/ab_$m.json 2> $O/ab_$m.err || { echo "BENCH $m FAILED"; tail -5 $O/ab_$m.err; exit 1; }
+  python3 -c "import json,sys; d=json.load(open('$O/ab_$m.json')); print('$VAR=$m', d['ms_per_step'], {k: v['ms'] for k, v in d['kernels'].items()})"
 done

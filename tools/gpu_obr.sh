@@ -11,7 +11,7 @@ rc=$?
 grep -E "FAILED|ERROR" $OUT/tests.log | head -20
 tail -2 $OUT/tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "TESTS_ABORTED rc=$rc"; exit 1; fi
-timeout -k 10 400 python bench.py --cpu-baseline off > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --cpu-baseline off > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'ms', d['ms_per_step'], {k: v['ms'] for k, v in d['kernels'].items()}, 'train', d.get('train', {}).get('value'))"

@@ -15,7 +15,7 @@ done
 cd /tmp && export TMPDIR=/tmp
 for b in $BUILDS; do
   name=${b%%=*}; lib=$R/differential_transformer_replication_amd/${b#*=}
-  DTA_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$name -o run -- python3 $R/bench.py --cpu-baseline off --train-steps 0 --no-configs --no-hbm --steps 3 --warmup 1 > $OUT/fetch_$name.log 2>&1 || { echo "PMC_FAILED $name"; tail -5 $OUT/fetch_$name.log; exit 1; }
+  DTA_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$name -o run -- python3 $R/bench.py --full --cpu-baseline off --train-steps 0 --no-configs --no-hbm --steps 3 --warmup 1 > $OUT/fetch_$name.log 2>&1 || { echo "PMC_FAILED $name"; tail -5 $OUT/fetch_$name.log; exit 1; }
   python3 - <<EOF
 import csv, glob, collections
 v = collections.defaultdict(list)

@@ -16,9 +16,9 @@ if [ "$2" != "skip-tests" ]; then
   tail -3 $OUT/tests.log
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "TESTS_ABORTED rc=$rc"; exit 1; fi
 fi
-timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -30 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
-PB="--cpu-baseline off --train-steps 0"
+PB="--full --cpu-baseline off --train-steps 0"
 # counter passes: the cfg2 core only (PMC summaries are keyed by kernel family + shape)
 PC="$PB --no-configs"
 cd /tmp && export TMPDIR=/tmp
