@@ -225,9 +225,10 @@ class AlternatingDiffTransformer(nn.Module):
         return logits, loss
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens):
+    def generate(self, idx, max_new_tokens, prefill_chunk=None):
+        kv_cache.check_prefill_chunk(prefill_chunk)      # bounds the prompt's prefill (cached path only)
         if kv_cache.enabled(idx):                        # KV-cache decode
-            return kv_cache.cached_generate(self, idx, max_new_tokens)
+            return kv_cache.cached_generate(self, idx, max_new_tokens, prefill_chunk)
         for _ in range(max_new_tokens):
             logits, _ = self(idx[:, -self.block_size:])
             probs = F.softmax(logits[:, -1, :], dim=-1)

@@ -19,14 +19,15 @@ LIB_PATH = os.environ.get("DTA_LIB", os.path.join(_HERE, "lib", "libdiffattn.so"
 DTA_BF16, DTA_F16, DTA_F32 = 0, 1, 2
 _DTYPES = {torch.bfloat16: DTA_BF16, torch.float16: DTA_F16, torch.float32: DTA_F32}
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # every symbol include/diffattn.h declares
 EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_attn_bwd_dcoef_partial_bytes",
            "dta_ln_fwd", "dta_ln_bwd", "dta_ln_bwd_workspace_bytes",
            "dta_rope", "dta_cast_f32", "dta_error_string", "dta_abi_version", "dta_supported",
            "dta_attn_decode", "dta_attn_decode_workspace_bytes", "dta_swiglu_fwd", "dta_swiglu_bwd",
-           "dta_accumulate_f32", "dta_swiglu_bwd_workspace_bytes", "dta_attn_bwd_dkdv_groups")
+           "dta_accumulate_f32", "dta_swiglu_bwd_workspace_bytes", "dta_attn_bwd_dkdv_groups",
+           "dta_attn_extend", "dta_extend_supported")
 
 
 class DtaTensor(ctypes.Structure):
@@ -102,6 +103,15 @@ class DecodeArgs(ctypes.Structure):
                 ("coef", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("length_dev", ctypes.c_void_p)]
 
 
+class ExtendArgs(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
+                ("Tq", ctypes.c_int32), ("pos", ctypes.c_int32), ("t_cap", ctypes.c_int32),
+                ("scale", ctypes.c_float),
+                ("q", DtaTensor), ("k_cache", DtaTensor), ("v_cache", DtaTensor), ("o", DtaTensor),
+                ("coef", ctypes.c_void_p)]
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -131,6 +141,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                                            ctypes.c_void_p]
         lib.dta_attn_decode.argtypes = [P(DecodeArgs), ctypes.c_void_p]
         lib.dta_attn_decode_workspace_bytes.argtypes = [ctypes.c_int32] * 6
+        lib.dta_attn_extend.argtypes = [P(ExtendArgs), ctypes.c_void_p]
+        lib.dta_extend_supported.argtypes = [ctypes.c_int32] * 4
         lib.dta_attn_decode_workspace_bytes.restype = ctypes.c_size_t
         lib.dta_attn_bwd_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         lib.dta_attn_bwd_workspace_bytes.restype = ctypes.c_size_t
@@ -144,7 +156,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.dta_attn_bwd_dkdv_groups.argtypes = [ctypes.c_int32] * 5
         for fn in ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_decode", "dta_ln_fwd", "dta_ln_bwd", "dta_rope", "dta_cast_f32",
                    "dta_abi_version", "dta_supported", "dta_swiglu_fwd", "dta_swiglu_bwd", "dta_accumulate_f32",
-                   "dta_attn_bwd_dkdv_groups"):
+                   "dta_attn_bwd_dkdv_groups", "dta_attn_extend", "dta_extend_supported"):
             getattr(lib, fn).restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")

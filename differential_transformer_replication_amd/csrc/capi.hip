@@ -504,4 +504,25 @@ int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
   return status(launch_decode(a->dtype, p, (hipStream_t)stream));
 }
 
+int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
+  return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
+}
+
+int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
+  if (!a || !ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (!extend_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
+  if (a->pos < 0 || a->t_cap < 0 || (int64_t)a->pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
+  if (a->Tq == 0 || (int64_t)a->B * a->H == 0) return DTA_OK;
+  // every operand is read or written by 16-byte vector accesses (O by 8-byte ones)
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->k_cache, a->dtype, true) ||
+      !ok_tensor(a->v_cache, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef)
+    return DTA_ERR_INVALID;
+  ExtendParams p{};
+  p.q = t5(a->q); p.k = t5(a->k_cache); p.v = t5(a->v_cache); p.o = t5(a->o);
+  p.coef = a->coef;
+  p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
+  p.Tq = a->Tq; p.pos = a->pos; p.sl2 = a->scale * kLog2e;
+  return status(launch_extend(a->dtype, p, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -120,6 +120,17 @@ struct DecodeParams {
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
+
+struct ExtendParams {
+  T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid
+  const float* coef;   // [h][i]
+  int B, H, N, HS, DV;
+  int Tq, pos;         // query row r sits at absolute position pos + r
+  float sl2;           // scale * log2(e)
+};
+
+int launch_extend(int dtype, const ExtendParams& p, hipStream_t st);   // extend.hip
+bool extend_supported(int dtype, int hs, int n, int dv);
 int launch_ln(int dtype, const LnParams& p, bool bwd, hipStream_t st);
 int launch_rope(int dtype, bool src_f32, const RopeParams& p, hipStream_t st);
 int launch_dcoef_reduce(const float* part, float* dcoef, int H, int N, int64_t per, hipStream_t st);

@@ -1,0 +1,314 @@
+// extend.hip -- multi-row differential attention over a KV cache, gfx950.
+//
+// Tq new query rows at absolute positions pos .. pos+Tq-1 against cache rows
+// 0 .. pos+Tq-1 (append to a live cache, scoring of candidate tokens, chunked
+// prefill).  For every (b, h) and row r < Tq
+//   o[b, r, h, :] = sum_i coef[h][i] softmax_j(q_i[r] . K_i[j] * scale, j <= pos + r) V[j, :]
+// i.e. rows pos .. of dta_attn_fwd at T = pos + Tq, inference only: nothing but O
+// is written (no O_i, no LSE, no workspace).
+//
+// The reference's own formulation (diff_transformer.py:57-72): combine the N
+// softmax maps first, then one @V.  Two passes over the key tiles:
+//   pass 1  per branch the running row max m_i and row sum l_i (no accumulator)
+//   merge   the workgroup's waves combine their (m_i, l_i) through LDS
+//   pass 2  S_i recomputed, P = sum_i coef_i / l_i * exp2(S_i * scale * log2e - m_i),
+//           packed once to the operand dtype, O^T += V^T P^T (one 32 x dv accumulator)
+// so registers do not depend on N (branches are streamed through one K_i tile),
+// and the partial accumulators of the waves add without a rescale (m_i is global
+// before pass 2 starts).
+//
+// Workgroup: one tile of 32 query rows; its NW (4, 2 or 1: what fits the LDS
+// budget) waves split the 32-key tiles between them (wave w takes tiles w, w+NW,
+// ...), each through its own K_i / V images, so a few new rows against a long
+// cache still fill the workgroup.  Matrix products are S^T = K_i Q_i^T and
+// O^T += V^T P^T on 32x32 MFMA tiles (a lane owns one query column).
+//
+// The cache tail (rows >= pos + Tq) may hold anything, NaN included: those K and V
+// rows are staged as zeros (a masked probability of 0 times a NaN V row inside an
+// MFMA would still be NaN), and the per-element mask j <= pos + r uses absolute
+// positions (pos is not tile aligned).  Every lane runs every transposed LDS read
+// (no divergence around them): tiles are padded to 32 rows, never masked by EXEC.
+#include "dta_common.h"
+#include "dta_internal.h"
+
+namespace dta {
+
+namespace {
+
+constexpr int kLdsBudget = 80 * 1024;        // two workgroups per CU
+
+struct ExtendPlan {
+  int nw;                // waves per workgroup
+  bool qlds;             // Q tile staged in LDS (else operand reads go to global / L1)
+  int tiles_off, q_off;  // byte offsets into the dynamic LDS
+  int tile_bytes;        // one wave's K_i + V images
+  int bytes;             // total
+};
+
+// LDS: fp32 stats [nw][N][2][32] | fp32 final (m_i, coef_i / l_i) [N][2][32] |
+// nw x (K_i image 32 x (HS + pad), V image 32 x (DV + pad)) | Q images [N][32][HS + pad].
+// The waves' accumulators are reduced through the tile region (32 x DV fp32).
+template <class E>
+bool extend_plan(int N, int HS, int DV, ExtendPlan& pl) {
+  const int es = (int)sizeof(E), pad = Pad<E>::v;
+  pl.tile_bytes = 32 * (HS + pad + DV + pad) * es;
+  const int qbytes = N * 32 * (HS + pad) * es;
+  const int red = 32 * DV * 4;
+  for (int nw = 4; nw >= 1; nw >>= 1) {
+    const int head = (nw + 1) * N * 2 * 32 * 4;
+    int tiles = nw * pl.tile_bytes;
+    if (nw > 1 && tiles < red) tiles = red;
+    if (head + tiles > kLdsBudget && nw > 1) continue;
+    pl.nw = nw;
+    pl.tiles_off = head;
+    pl.q_off = head + tiles;
+    pl.qlds = pl.q_off + qbytes <= kLdsBudget;
+    pl.bytes = pl.q_off + (pl.qlds ? qbytes : 0);
+    return pl.bytes <= 160 * 1024;
+  }
+  return false;
+}
+
+// wave-private LDS images: the wave's own writes must be visible to its other
+// lanes' reads (DS operations of one wave complete in order)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// one wave stages 32 rows x C columns (row j0 + r of the cache; zero when >= L)
+template <class E>
+__device__ __forceinline__ void stage_rows(E* img, int stride, const E* src, int64_t st, int C, int j0, int L,
+                                           int lane) {
+  constexpr int VEC = Ops<E>::VEC;
+  const int cpr = C / VEC;
+  for (int x = lane; x < 32 * cpr; x += 64) {
+    const int r = x / cpr, c = (x - r * cpr) * VEC;
+    const bool ok = j0 + r < L;
+    stage_vec<E>(img + r * stride + c, src + (int64_t)(ok ? j0 + r : 0) * st + c, ok);
+  }
+}
+
+template <class E, int NDB, bool QLDS>
+__global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_off, int q_off, int tile_bytes) {
+  using O = Ops<E>;
+  using frag = typename O::frag;
+  constexpr int SPB = 32 / O::KSTEP;            // k-steps of one 32-key tile in the PV product
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  const int hf = lane >> 5, c32 = lane & 31;
+  const int h = blockIdx.y, b = blockIdx.z;
+  const int N = p.N, HS = p.HS, DV = p.DV;
+  const int kstr = HS + Pad<E>::v, vstr = DV + Pad<E>::v;
+  const int nsq = HS / O::KSTEP, ndb = DV >> 5;
+  const int r0 = blockIdx.x * 32;               // first query row of the tile
+  const int L = p.pos + p.Tq;                   // valid cache rows
+  const int q0 = p.pos + r0;                    // absolute position of the tile's first row
+  const int qlim = min(q0 + c32, L - 1);        // this lane's query sees keys <= qlim
+  const int ntiles = (min(q0 + 32, L) + 31) >> 5;
+
+  float* stats = reinterpret_cast<float*>(smem) + wave * N * 64;       // [i][m | l][32], this wave's
+  float* fin = reinterpret_cast<float*>(smem) + nw * N * 64;           // [i][m | coef / l][32]
+  E* Kw = reinterpret_cast<E*>(smem + tiles_off + wave * tile_bytes);
+  E* Vw = Kw + 32 * kstr;
+  E* Qs = reinterpret_cast<E*>(smem + q_off);
+
+  const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh;
+  const E* gk = reinterpret_cast<const E*>(p.k.p) + b * p.k.sb + h * p.k.sh;
+  const E* gv = reinterpret_cast<const E*>(p.v.p) + b * p.v.sb + h * p.v.sh;
+
+  // rows past Tq of a partial query tile read the last valid row (never stored)
+  if constexpr (QLDS) {
+    constexpr int VEC = O::VEC;
+    const int cpr = HS / VEC;
+    for (int x = tid; x < N * 32 * cpr; x += blockDim.x) {
+      const int ir = x / cpr, c = (x - ir * cpr) * VEC;
+      const int i = ir >> 5, r = ir & 31;
+      stage_vec<E>(Qs + ir * kstr + c, gq + (int64_t)min(r0 + r, p.Tq - 1) * p.q.st + i * p.q.si + c, true);
+    }
+  }
+  for (int i = 0; i < N; ++i) {
+    stats[i * 64 + c32] = -INFINITY;
+    stats[i * 64 + 32 + c32] = 0.f;
+  }
+  __syncthreads();
+
+  auto qrow = [&](int i) -> const E* {
+    if constexpr (QLDS) return Qs + (i * 32 + c32) * kstr;
+    else return gq + (int64_t)min(r0 + c32, p.Tq - 1) * p.q.st + i * p.q.si;
+  };
+  // S^T (keys x queries) of branch i against the staged K_i image, in log2 units;
+  // masked: key kt*32 + rowof(r, hf) above this lane's query position -> -inf
+  auto scores = [&](int i, int kt, bool masked) -> f32x16 {
+    const E* kr = Kw + c32 * kstr;
+    const E* qr = qrow(i);
+    f32x16 sa = {};
+#pragma unroll 4
+    for (int s = 0; s < nsq; ++s) sa = O::mma(O::row(kr, s, hf), O::row(qr, s, hf), sa);
+    const int lim = qlim - kt * 32 - 4 * hf;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float t = sa[r] * p.sl2;
+      sa[r] = (masked && (r & 3) + 8 * (r >> 2) > lim) ? -INFINITY : t;
+    }
+    return sa;
+  };
+
+  // ---- pass 1: running (m_i, l_i) of this wave's key tiles
+  for (int kt = wave; kt < ntiles; kt += nw) {
+    const bool masked = kt * 32 + 31 > q0;
+    for (int i = 0; i < N; ++i) {
+      wave_sync();                                 // the previous image's reads are done
+      stage_rows<E>(Kw, kstr, gk + i * p.k.si, p.k.st, HS, kt * 32, L, lane);
+      wave_sync();
+      const f32x16 sa = scores(i, kt, masked);
+      float mt = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mt = fmaxf(mt, sa[r]);
+      mt = wave_max_halves(mt);
+      const float mo = stats[i * 64 + c32], lo = stats[i * 64 + 32 + c32];
+      const float mn = fmaxf(mo, mt);
+      const float ms = mn == -INFINITY ? 0.f : mn;  // a tile wholly above the row: no NaN from inf - inf
+      float sum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sum += exp2_fast(sa[r] - ms);
+      sum = wave_sum_halves(sum);
+      stats[i * 64 + c32] = mn;
+      stats[i * 64 + 32 + c32] = fmaf(lo, exp2_fast(mo - ms), sum);
+    }
+  }
+  __syncthreads();
+
+  // ---- merge: global m_i and coef_i / l_i per query row (tile 0 holds key 0, so m_i is finite)
+  {
+    const float* all = reinterpret_cast<const float*>(smem);
+    for (int x = tid; x < N * 32; x += blockDim.x) {
+      const int i = x >> 5, q = x & 31;
+      float M = -INFINITY;
+      for (int w = 0; w < nw; ++w) M = fmaxf(M, all[(w * N + i) * 64 + q]);
+      float l = 0.f;
+      for (int w = 0; w < nw; ++w)
+        l = fmaf(all[(w * N + i) * 64 + 32 + q], exp2_fast(all[(w * N + i) * 64 + q] - M), l);
+      fin[i * 64 + q] = M;
+      fin[i * 64 + 32 + q] = p.coef[h * N + i] / l;
+    }
+  }
+  __syncthreads();
+
+  // ---- pass 2: combined probabilities, one PV product
+  f32x16 acc[NDB];
+#pragma unroll
+  for (int d = 0; d < NDB; ++d) acc[d] = f32x16{};
+  for (int kt = wave; kt < ntiles; kt += nw) {
+    const bool masked = kt * 32 + 31 > q0;
+    wave_sync();
+    stage_rows<E>(Vw, vstr, gv, p.v.st, DV, kt * 32, L, lane);
+    f32x16 pt = {};
+    for (int i = 0; i < N; ++i) {
+      wave_sync();
+      stage_rows<E>(Kw, kstr, gk + i * p.k.si, p.k.st, HS, kt * 32, L, lane);
+      wave_sync();
+      const f32x16 sa = scores(i, kt, masked);
+      const float mi = fin[i * 64 + c32], ci = fin[i * 64 + 32 + c32];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) pt[r] = fmaf(ci, exp2_fast(sa[r] - mi), pt[r]);
+    }
+    frag pf[SPB];
+    if constexpr (SPB == 2) {
+      pf[0] = O::template pack<0>(pt);
+      pf[1] = O::template pack<1>(pt);
+    } else {
+#pragma unroll
+      for (int s = 0; s < SPB; ++s) pf[s] = pt[s];
+    }
+    wave_sync();                                   // V image (staged before the branch loop)
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+      if (d < ndb) {                               // uniform: every lane runs the transposed reads
+#pragma unroll
+        for (int s = 0; s < SPB; ++s) acc[d] = O::mma(O::tr_perm(Vw + d * 32, vstr, s, hf, lane), pf[s], acc[d]);
+      }
+  }
+
+  // ---- the waves' partial accumulators add up in wave 0 (through the tile region)
+  float* red = reinterpret_cast<float*>(smem + tiles_off);
+  for (int w = 1; w < nw; ++w) {
+    __syncthreads();
+    if (wave == w) {
+#pragma unroll
+      for (int d = 0; d < NDB; ++d)
+        if (d < ndb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) red[(d * 16 + r) * 64 + lane] = acc[d][r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int d = 0; d < NDB; ++d)
+        if (d < ndb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[d][r] += red[(d * 16 + r) * 64 + lane];
+    }
+  }
+  // O^T: registers 4g..4g+3 of block d = columns 32d + 8g + 4hf .. +3 of query row c32
+  if (wave == 0 && r0 + c32 < p.Tq) {
+    E* go = reinterpret_cast<E*>(p.o.p) + b * p.o.sb + (int64_t)(r0 + c32) * p.o.st + h * p.o.sh;
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+      if (d < ndb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          store4<E>(go + d * 32 + 8 * g + 4 * hf, acc[d][4 * g], acc[d][4 * g + 1], acc[d][4 * g + 2], acc[d][4 * g + 3]);
+  }
+}
+
+template <class E, int NDB, bool QLDS>
+int extend_go(const ExtendParams& p, const ExtendPlan& pl, hipStream_t st) {
+  auto kern = extend_kernel<E, NDB, QLDS>;
+  // more than the default dynamic LDS limit: raised once per instantiation
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (attr != hipSuccess) return (int)attr;
+  const dim3 grid((p.Tq + 31) / 32, p.H, p.B);
+  hipLaunchKernelGGL(kern, grid, dim3(pl.nw * 64), pl.bytes, st, p, pl.tiles_off, pl.q_off, pl.tile_bytes);
+  return (int)hipGetLastError();
+}
+
+template <class E>
+int extend_launch(const ExtendParams& p, hipStream_t st) {
+  ExtendPlan pl;
+  if (!extend_plan<E>(p.N, p.HS, p.DV, pl)) return -2;
+  const int ndb = p.DV / 32;
+  if (pl.qlds) {
+    if (ndb <= 2) return extend_go<E, 2, true>(p, pl, st);
+    if (ndb <= 4) return extend_go<E, 4, true>(p, pl, st);
+    return extend_go<E, 8, true>(p, pl, st);
+  }
+  if (ndb <= 2) return extend_go<E, 2, false>(p, pl, st);
+  if (ndb <= 4) return extend_go<E, 4, false>(p, pl, st);
+  return extend_go<E, 8, false>(p, pl, st);
+}
+
+}  // namespace
+
+bool extend_supported(int dtype, int hs, int n, int dv) {
+  if (dtype < 0 || dtype > 2) return false;
+  if (hs < 16 || hs > 128 || hs % 16 || dv < 32 || dv > 256 || dv % 32 || n < 1 || n > 8) return false;
+  ExtendPlan pl;
+  return dtype == 2 ? extend_plan<float>(n, hs, dv, pl) : extend_plan<__bf16>(n, hs, dv, pl);
+}
+
+int launch_extend(int dtype, const ExtendParams& p, hipStream_t st) {
+  if ((int64_t)p.B * p.H * p.Tq == 0) return 0;
+  if (!extend_supported(dtype, p.HS, p.N, p.DV)) return -2;
+  switch (dtype) {
+    case 0: return extend_launch<__bf16>(p, st);
+    case 1: return extend_launch<_Float16>(p, st);
+    case 2: return extend_launch<float>(p, st);
+  }
+  return -2;
+}
+
+}  // namespace dta

@@ -21,6 +21,13 @@ full-recompute path whenever the logits agree to sampling precision.
 captured HIP graph of the whole model step (the position lives on the device,
 ``dta_attn_decode`` reads its length there); ``DTA_DECODE_GRAPH=0`` launches
 them eagerly instead.
+
+Between the prefill and the one-token step sits the multi-row step: several new
+positions at once against the live cache (``append_logits``: a second chat turn,
+a tool result, the scoring of candidate tokens with ``all_rows=True``), through
+``ops.diff_attention_extend``, which writes nothing but its output.  The same step
+prefills a long prompt in bounded memory (``prefill_chunk``): the first chunk runs
+the fused training forward, every further chunk appends.
 """
 from __future__ import annotations
 
@@ -33,7 +40,8 @@ from torch.nn import functional as F
 from . import ops
 from ._compat import mha_out_scale
 
-__all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled"]
+__all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
+           "prefill_logits", "check_prefill_chunk"]
 
 
 def enabled(idx: torch.Tensor, model=None) -> bool:
@@ -115,9 +123,11 @@ def _attention_step(block, x: torch.Tensor, layer: int, cache: KVCache, pos: int
         else:
             k_rows[:, :Tn].copy_(src)
         buf[:, :Tn, nq:].copy_(qkv[..., 2 * nq:])
+    elif not isinstance(pos, DevicePosition) and Tn != 1:
+        out = _extend_rows(qkv, buf, coef, freqs, H, N, hs, dv, pos)
     else:
         if Tn != 1:
-            raise RuntimeError("decode steps take one new position at a time")
+            raise RuntimeError("graph decode steps take one new position at a time")
         dev = isinstance(pos, DevicePosition)
         q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))               # (B, 1, H, N, hs)
         k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
@@ -142,6 +152,33 @@ def _attention_step(block, x: torch.Tensor, layer: int, cache: KVCache, pos: int
         gn = attn.group_norm
         out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
     return attn.dropout(attn.proj(out))
+
+
+def _extend_rows(qkv, buf, coef, freqs, H: int, N: int, hs: int, dv: int, pos: int) -> torch.Tensor:
+    """Attention of the Tn new rows at positions pos .. pos+Tn-1 (pos > 0, host
+    integer): their K_i / V rows go into the cache first, then one
+    ``diff_attention_extend`` launch; head sizes it has no plan for (40, 72: not a
+    multiple of 16) take one decode launch per row instead -- correct, but the cache
+    is read once per row."""
+    B, Tn, _ = qkv.shape
+    nq = H * N * hs
+    q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
+    k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
+    k_rows = buf[..., :nq].unflatten(-1, (H, N, hs))
+    v_rows = buf[..., nq:].unflatten(-1, (H, dv))
+    if freqs is not None:
+        tab = freqs[pos:pos + Tn]
+        q_rot = torch.empty_like(q)
+        ops.rope_rows(q, q_rot, tab)
+        ops.rope_rows(k_new, k_rows[:, pos:pos + Tn], tab)
+        q = q_rot
+    else:
+        k_rows[:, pos:pos + Tn].copy_(k_new)
+    buf[:, pos:pos + Tn, nq:].copy_(qkv[..., 2 * nq:])
+    if ops.extend_supported(qkv.dtype, hs, N, dv):
+        return ops.diff_attention_extend(q, k_rows, v_rows, coef, pos)
+    rows = [ops.diff_attention_decode(q[:, r], k_rows, v_rows, coef, pos + r + 1) for r in range(Tn)]
+    return torch.stack(rows, dim=1)
 
 
 class DevicePosition:
@@ -183,9 +220,10 @@ class DecodeGraph:
         return self.logits.clone()
 
 
-def _model_step(model, idx: torch.Tensor, cache: KVCache, pos: int) -> torch.Tensor:
+def _model_step(model, idx: torch.Tensor, cache: KVCache, pos: int, all_rows: bool = False) -> torch.Tensor:
     """The model's forward (diff_transformer.py:154-175 / Ndiff_transformer.py) over
-    positions pos .. pos+T-1 of the window; returns the last row of logits."""
+    positions pos .. pos+T-1 of the window; returns the last row of logits (B, vocab),
+    or with ``all_rows`` every row's (B, T, vocab)."""
     T = idx.shape[1]
     x = model.token_embedding_table(idx)
     if hasattr(model, "position_embedding_table"):
@@ -194,6 +232,8 @@ def _model_step(model, idx: torch.Tensor, cache: KVCache, pos: int) -> torch.Ten
     for layer, block in enumerate(model.blocks, 1):
         x = x + _attention_step(block, block.ln1(x), layer, cache, pos)
         x = x + block.ffwd(block.ln2(x))
+    if all_rows:
+        return model.lm_head(model.ln_f(x))
     return model.lm_head(model.ln_f(x[:, -1:]))[:, -1]
 
 
@@ -219,10 +259,73 @@ def last_logits(model, idx: torch.Tensor, cache: KVCache) -> torch.Tensor:
     return logits
 
 
+def append_logits(model, new_idx: torch.Tensor, cache: KVCache, all_rows: bool = False) -> torch.Tensor:
+    """Feed ``new_idx`` (B, Tn >= 1) as the tokens at positions ``cache.length ..
+    cache.length+Tn-1`` of a live cache (one multi-row step per layer instead of a
+    re-prefill of the whole window) and advance ``cache.length``.  Returns the last
+    row's logits (B, vocab), or with ``all_rows`` the logits of all Tn rows
+    (B, Tn, vocab): row r is the distribution of the token after ``new_idx[:, r]``,
+    which scores a continuation or verifies speculated tokens in one step.
+
+    Positions are absolute within the window, so an append cannot cross
+    ``block_size``: the slide would move every cached row, and the caller re-prefills
+    through ``last_logits``.  ``last_logits`` continues single-token decode afterwards
+    (same cache buffers, so a captured decode graph stays valid)."""
+    if new_idx.dim() != 2 or new_idx.shape[1] < 1:
+        raise ValueError("new_idx must be (B, Tn) with Tn >= 1")
+    Tn, bs = new_idx.shape[1], model.block_size
+    if cache.length == 0:
+        raise ValueError("append_logits needs a prefilled cache: run last_logits on the prompt first")
+    if cache.length + Tn > bs:
+        raise ValueError(f"appending {Tn} tokens at length {cache.length} crosses block_size {bs}: "
+                         "re-prefill the slid window through last_logits")
+    for buf in cache.rows.values():
+        if buf.shape[0] != new_idx.shape[0]:
+            raise ValueError(f"batch size {new_idx.shape[0]} differs from the cache's {buf.shape[0]}")
+    if all_rows:
+        logits = _model_step(model, new_idx, cache, cache.length, all_rows=True)
+    else:
+        logits = _model_step(model, new_idx, cache, cache.length)
+    cache.length += Tn
+    if cache.length >= bs:
+        cache.length = 0                      # a full window slides next step
+    return logits
+
+
+def check_prefill_chunk(prefill_chunk) -> None:
+    if prefill_chunk is not None and prefill_chunk < 1:
+        raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+
+
+def prefill_logits(model, idx: torch.Tensor, cache: KVCache, prefill_chunk=None) -> torch.Tensor:
+    """Prefill ``cache`` with the window of ``idx`` and return its newest position's
+    logits.  ``prefill_chunk = C``: the first min(C, T) tokens run the fused training
+    forward (which saves its backward tensors), the rest go in chunks of at most C
+    through ``append_logits``, so no step holds more than C rows of activations.
+    ``None``: ``last_logits``'s one-shot prefill."""
+    check_prefill_chunk(prefill_chunk)
+    cache.length = 0
+    if prefill_chunk is None:
+        return last_logits(model, idx, cache)
+    cond = idx[:, -model.block_size:]
+    T = cond.shape[1]
+    first = min(prefill_chunk, T)
+    logits = _model_step(model, cond[:, :first], cache, 0)
+    cache.length = first if first < model.block_size else 0
+    for s in range(first, T, prefill_chunk):
+        logits = append_logits(model, cond[:, s:s + prefill_chunk], cache)
+    return logits
+
+
 @torch.no_grad()
-def cached_generate(model, idx: torch.Tensor, max_new_tokens: int) -> torch.Tensor:
+def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk=None) -> torch.Tensor:
+    check_prefill_chunk(prefill_chunk)
     cache = KVCache()
     for _ in range(max_new_tokens):
-        probs = F.softmax(last_logits(model, idx, cache), dim=-1)
+        if prefill_chunk is not None and (cache.length == 0 or idx.shape[1] != cache.length + 1):
+            logits = prefill_logits(model, idx, cache, prefill_chunk)
+        else:
+            logits = last_logits(model, idx, cache)
+        probs = F.softmax(logits, dim=-1)
         idx = torch.cat((idx, torch.multinomial(probs, num_samples=1)), dim=1)
     return idx

@@ -723,3 +723,49 @@ def diff_attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
                         None if length_dev is None else length_dev.data_ptr())
     _lib.check(lib.dta_attn_decode(a, _lib.stream_handle(q.device)))
     return o.view(B, H * dv)
+
+
+# ------------------------------------------------------------------ extend ---
+def extend_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
+    """Whether ``diff_attention_extend`` has a kernel plan for this shape
+    (dta_extend_supported): hs % 16 == 0 in 16..128, dv % 32 == 0 up to 256, N <= 8."""
+    return bool(_lib.load().dta_extend_supported(_lib.dtype_code(dtype), hs, N, dv))
+
+
+def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: int) -> Tensor:
+    """``Tq`` new query rows at absolute positions ``pos .. pos+Tq-1`` against the
+    cache rows ``0 .. pos+Tq-1`` (the new rows' own K_i / V already written there):
+    o[b, r] = sum_i coef[h,i] softmax_j(q_i[b,r] K_i[b,j]^T / sqrt(hs), j <= pos + r) V[b,j].
+
+    q: (B, Tq, H, N, hs), rotated already for RoPE models; k_cache: (B, T_cap, H, N, hs);
+    v_cache: (B, T_cap, H, dv) (strided views, innermost dim contiguous).  Returns
+    (B, Tq, H*dv): rows ``pos:`` of ``diff_attention`` over the same ``pos + Tq``
+    positions, with nothing saved for a backward.  Cache rows past ``pos + Tq`` may hold
+    anything.  Raises for a shape without a kernel plan (``extend_supported``): there is
+    no fallback here."""
+    lib = _lib.load()
+    _require_gpu(q, k_cache, v_cache, coef)
+    if q.dim() != 5:
+        raise RuntimeError("q must be (B, Tq, H, N, hs)")
+    B, Tq, H, N, hs = q.shape
+    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
+    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
+        raise RuntimeError("k_cache/v_cache shapes do not match q")
+    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
+        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+    if tuple(coef.shape) != (H, N):
+        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+    pos = int(pos)
+    if pos < 0 or pos + Tq > T_cap:
+        raise RuntimeError(f"extend rows {pos}..{pos + Tq - 1} outside the cache's {T_cap} rows")
+    if not extend_supported(q.dtype, hs, N, dv):
+        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
+    if B * Tq == 0:
+        return o.view(B, Tq, H * dv)
+    a = _lib.ExtendArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, pos, T_cap, 1.0 / math.sqrt(hs),
+                        _lib.tensor5(q), _lib.tensor5(k_cache), _lib.tensor5(v_cache), _lib.tensor5(o),
+                        coef.data_ptr())
+    _lib.check(lib.dta_attn_extend(a, _lib.stream_handle(q.device)))
+    return o.view(B, Tq, H * dv)

@@ -43,7 +43,8 @@
 extern "C" {
 #endif
 
-#define DTA_ABI_VERSION 8   /* 8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
+#define DTA_ABI_VERSION 9   /* 9: dta_attn_extend (several new rows over the KV cache), dta_extend_supported;
+                               8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
                                5: RoPE of Q_i at the forward's load (rope_freqs, q_rot);
@@ -271,6 +272,40 @@ typedef struct dta_attn_decode_args {
 int dta_attn_decode(const dta_attn_decode_args* a, void* stream);
 size_t dta_attn_decode_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, int32_t head_size, int32_t dv,
                                        int32_t t_cap);
+
+/* Several new rows over a KV cache (ABI 9): append to a live cache, scoring of
+ * candidate tokens, chunked prefill.  Replaces DiffHead.forward's scores / mask /
+ * softmax / combine / @V (diff_transformer.py:57-72; Ndiff_transformer.py:102-125)
+ * for the Tq NEWEST rows of the window only: query row r sits at absolute position
+ * pos + r and for every (b, h)
+ *   o[b][r][h] = sum_i coef[h][i] * softmax_j(q_i[b][r][h] . K_i[b][j][h] * scale, j <= pos + r) V[b][j][h]
+ * which is rows pos .. pos+Tq-1 of dta_attn_fwd's output at T = pos + Tq, and with
+ * Tq = 1 dta_attn_decode at length = pos + 1.  Inference only: nothing but o is
+ * written (no Obr, no LSE, no dropout, no workspace).
+ * Mask: key j is kept for row r iff j <= pos + r (absolute positions; pos need
+ * not be a multiple of any tile size).  Cache rows 0 .. pos+Tq-1 must be valid --
+ * the new rows' own K_i / V are written by the caller first; rows pos+Tq .. t_cap-1
+ * may hold anything, NaN included: they are never multiplied into the result.
+ * q [b][t < Tq][h][i][d] (rotated already for RoPE models), k_cache [b][t][h][i][d],
+ * v_cache [b][t][h][e] (strided views of the packed cache buffer, as for decode),
+ * o [b][t < Tq][h][e].  head_size % 16 == 0, 16 <= head_size <= 128; dv % 32 == 0,
+ * dv <= 256; 1 <= n_terms <= 8; every dtype; every tensor 16-byte aligned with
+ * strides that are multiples of 16 bytes; anything else is DTA_ERR_UNSUPPORTED
+ * (dta_extend_supported tells beforehand).  Tq == 0 or B*H == 0: DTA_OK, no launch.
+ * pos < 0, pos + Tq > t_cap, a null pointer or a misaligned stride: DTA_ERR_INVALID. */
+typedef struct dta_attn_extend_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* new query rows */
+  int32_t pos;               /* absolute position of query row 0; keys 0 .. pos+Tq-1 are valid */
+  int32_t t_cap;             /* rows of the cache views (>= pos + Tq) */
+  float scale;
+  dta_tensor q, k_cache, v_cache, o;
+  const float* coef;         /* fp32 [h][i] */
+} dta_attn_extend_args;
+int dta_attn_extend(const dta_attn_extend_args* a, void* stream);
+int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every
