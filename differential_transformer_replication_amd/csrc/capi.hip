@@ -484,8 +484,11 @@ size_t dta_attn_decode_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, in
   return single > split ? single : split;
 }
 
-int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
-  if (!a || !ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+// dta_attn_decode and dta_attn_decode_ragged: one validation, one launch path.  ldev / lsb:
+// the device length(s) and their batch stride (0: one value, 1: int32 [B]).
+extern "C++" template <class A>
+static int decode_call(const A* a, const int32_t* ldev, int lsb, void* stream) {
+  if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (a->head_size % 8 || a->head_size > 128 || a->n_terms > 4 || a->dv > 256) return DTA_ERR_UNSUPPORTED;
   if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
   if ((int64_t)a->B * a->H == 0) return DTA_OK;
@@ -498,20 +501,32 @@ int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
   p.q = t5(a->q); p.k = t5(a->k_cache); p.v = t5(a->v_cache); p.o = t5(a->o);
   p.coef = a->coef; p.ws = a->workspace;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
-  p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = a->length_dev;
+  p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = ldev; p.Lsb = lsb;
   p.S = (int)decode_splits(a->length);
   p.ml = a->workspace + (int64_t)a->B * a->H * p.S * a->n_terms * a->dv;   // after the partial rows
   return status(launch_decode(a->dtype, p, (hipStream_t)stream));
+}
+
+int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
+  if (!a) return DTA_ERR_INVALID;
+  return decode_call(a, a->length_dev, 0, stream);
+}
+
+int dta_attn_decode_ragged(const dta_attn_decode_ragged_args* a, void* stream) {
+  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4) return DTA_ERR_INVALID;
+  return decode_call(a, a->lengths_dev, 1, stream);
 }
 
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }
 
-int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
-  if (!a || !ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+// dta_attn_extend and dta_attn_extend_ragged: one validation, one launch path.
+extern "C++" template <class A>
+static int extend_call(const A* a, int pos, const int32_t* pos_dev, const int32_t* cnt_dev, void* stream) {
+  if (!ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (!extend_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
-  if (a->pos < 0 || a->t_cap < 0 || (int64_t)a->pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
+  if (pos < 0 || a->t_cap < 0 || (int64_t)pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
   if (a->Tq == 0 || (int64_t)a->B * a->H == 0) return DTA_OK;
   // every operand is read or written by 16-byte vector accesses (O by 8-byte ones)
   if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->k_cache, a->dtype, true) ||
@@ -521,8 +536,19 @@ int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
   p.q = t5(a->q); p.k = t5(a->k_cache); p.v = t5(a->v_cache); p.o = t5(a->o);
   p.coef = a->coef;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
-  p.Tq = a->Tq; p.pos = a->pos; p.sl2 = a->scale * kLog2e;
+  p.Tq = a->Tq; p.pos = pos; p.sl2 = a->scale * kLog2e;
+  p.pos_dev = pos_dev; p.cnt_dev = cnt_dev; p.cap = a->t_cap;
   return status(launch_extend(a->dtype, p, (hipStream_t)stream));
+}
+
+int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
+  if (!a) return DTA_ERR_INVALID;
+  return extend_call(a, a->pos, nullptr, nullptr, stream);
+}
+
+int dta_attn_extend_ragged(const dta_attn_extend_ragged_args* a, void* stream) {
+  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  return extend_call(a, 0, a->pos_dev, a->count_dev, stream);
 }
 
 }  // extern "C"

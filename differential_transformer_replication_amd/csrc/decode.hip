@@ -14,6 +14,8 @@
 //            (coalesced V rows), LDS reduction over the groups.
 // The split-key plan below is the one used for the standard head sizes.
 // Algorithmic bytes per (b, h) and token: L * (N*hs + dv) * sizeof(E).
+// Ragged batches (dta_attn_decode_ragged) run the same kernels with L read per
+// sequence (clamp_len): L = len_b above, and a length of 0 writes zeros.
 #include "dta_common.h"
 #include "dta_internal.h"
 
@@ -73,11 +75,12 @@ __device__ __forceinline__ void block_reduce(float (&v)[NB], float* red) {
   __syncthreads();
 }
 
-// The valid length: the device value when given, clamped to [0, L] (L = the host
-// upper bound the grid and workspace were sized for), so a bad device length can
+// The valid length of sequence b: the device value when given (one for the launch,
+// Lsb = 0, or one per sequence, Lsb = 1: ragged batches), clamped to [0, L] (L = the
+// host upper bound the grid and workspace were sized for), so a bad device length can
 // never index past the cache, the workspace or the combine's LDS weights.
-__device__ __forceinline__ int clamp_len(const DecodeParams& p) {
-  return p.Ldev ? min(max(*p.Ldev, 0), p.L) : p.L;
+__device__ __forceinline__ int clamp_len(const DecodeParams& p, int b) {
+  return p.Ldev ? min(max(p.Ldev[b * p.Lsb], 0), p.L) : p.L;
 }
 
 template <class E, int N>
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   __shared__ float red[kWaves * N];
   __shared__ float part[kThreads];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int HS = p.HS, DV = p.DV, L = clamp_len(p);
+  const int HS = p.HS, DV = p.DV, L = clamp_len(p, b);
   const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh;
   for (int x = tid; x < N * HS; x += kThreads) qs[x] = (float)gq[(x / HS) * p.q.si + x % HS];
   __syncthreads();
@@ -180,8 +183,9 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   __shared__ float part[G][N][DV + 4];
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j0 = s * kChunk, L = clamp_len(p);
-  if (j0 >= L) return;                         // grid sized for an upper bound (uniform exit)
+  const int j0 = s * kChunk, L = clamp_len(p, b);
+  if (j0 >= L) return;                         // grid sized for an upper bound; a chunk past its own
+                                               // sequence's length touches no memory (uniform exit)
   const int nk = min(kChunk, L - j0);
 
   // phase 1: scores of this chunk into LDS
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
   __shared__ float red[kWaves * N];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int64_t row0 = ((int64_t)b * p.H + h) * p.S;       // partial stride: the launch's S
-  const int S = min((clamp_len(p) + kChunk - 1) / kChunk, p.S);  // chunks written this call
+  const int S = min((clamp_len(p, b) + kChunk - 1) / kChunk, p.S);  // chunks written this call
   const float* ml = p.ml + row0 * N * 2;
   float M[N], Ls[N];
 #pragma unroll

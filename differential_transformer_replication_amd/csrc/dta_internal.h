@@ -117,6 +117,7 @@ struct DecodeParams {
   int B, H, N, HS, DV, L, ldw, S;   // L: length, or its upper bound when Ldev is set
   float scale;
   const int* Ldev;     // optional device length
+  int Lsb;             // batch stride of Ldev: 0 = one length for the launch, 1 = int32 [B] (ragged)
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
@@ -127,6 +128,10 @@ struct ExtendParams {
   int B, H, N, HS, DV;
   int Tq, pos;         // query row r sits at absolute position pos + r
   float sl2;           // scale * log2(e)
+  // ragged batches (dta_attn_extend_ragged; both NULL = the one-position launch above)
+  const int* pos_dev;  // int32 [B]: sequence b's pos, clamped to [0, cap - Tq]
+  const int* cnt_dev;  // optional int32 [B]: real rows of sequence b, clamped to [0, Tq]; rows past it are written as zeros
+  int cap;             // rows of the cache views (the clamp of pos_dev)
 };
 
 int launch_extend(int dtype, const ExtendParams& p, hipStream_t st);   // extend.hip

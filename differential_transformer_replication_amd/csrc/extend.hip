@@ -23,6 +23,13 @@
 // cache still fill the workgroup.  Matrix products are S^T = K_i Q_i^T and
 // O^T += V^T P^T on 32x32 MFMA tiles (a lane owns one query column).
 //
+// Ragged batches (dta_attn_extend_ragged) run the same kernel: pos and the number of
+// real rows come per sequence from device arrays (pos_b, count_b <= Tq), the valid
+// cache rows are 0 .. pos_b + count_b - 1, the key-tile loops stop at the sequence's
+// own last tile, rows count_b .. Tq-1 are written as zeros and a query tile without
+// a real row exits after writing them.  The one-position launch is pos_b = pos,
+// count_b = Tq: the same instructions on the same values, so equal bit for bit.
+//
 // The cache tail (rows >= pos + Tq) may hold anything, NaN included: those K and V
 // rows are staged as zeros (a masked probability of 0 times a NaN V row inside an
 // MFMA would still be NaN), and the per-element mask j <= pos + r uses absolute
@@ -104,8 +111,21 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   const int kstr = HS + Pad<E>::v, vstr = DV + Pad<E>::v;
   const int nsq = HS / O::KSTEP, ndb = DV >> 5;
   const int r0 = blockIdx.x * 32;               // first query row of the tile
-  const int L = p.pos + p.Tq;                   // valid cache rows
-  const int q0 = p.pos + r0;                    // absolute position of the tile's first row
+  // ragged batches: sequence b's own position and real row count, clamped so that no
+  // device value can index past the cache views (one-position launch: p.pos, Tq)
+  const int pos = p.pos_dev ? min(max(p.pos_dev[b], 0), p.cap - p.Tq) : p.pos;
+  const int cnt = p.cnt_dev ? min(max(p.cnt_dev[b], 0), p.Tq) : p.Tq;
+  if (r0 >= cnt) {                              // no real row in this tile (uniform): zeros, no cache read
+    const int cpr = DV / 4;
+    for (int x = tid; x < 32 * cpr; x += blockDim.x) {
+      const int r = r0 + x / cpr, c = (x % cpr) * 4;
+      if (r < p.Tq)
+        store4<E>(reinterpret_cast<E*>(p.o.p) + b * p.o.sb + (int64_t)r * p.o.st + h * p.o.sh + c, 0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
+  const int L = pos + cnt;                      // valid cache rows of this sequence (>= 1 here)
+  const int q0 = pos + r0;                      // absolute position of the tile's first row
   const int qlim = min(q0 + c32, L - 1);        // this lane's query sees keys <= qlim
   const int ntiles = (min(q0 + 32, L) + 31) >> 5;
 
@@ -119,14 +139,14 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   const E* gk = reinterpret_cast<const E*>(p.k.p) + b * p.k.sb + h * p.k.sh;
   const E* gv = reinterpret_cast<const E*>(p.v.p) + b * p.v.sb + h * p.v.sh;
 
-  // rows past Tq of a partial query tile read the last valid row (never stored)
+  // rows past the real ones of a partial query tile read the last real row (their result is never stored)
   if constexpr (QLDS) {
     constexpr int VEC = O::VEC;
     const int cpr = HS / VEC;
     for (int x = tid; x < N * 32 * cpr; x += blockDim.x) {
       const int ir = x / cpr, c = (x - ir * cpr) * VEC;
       const int i = ir >> 5, r = ir & 31;
-      stage_vec<E>(Qs + ir * kstr + c, gq + (int64_t)min(r0 + r, p.Tq - 1) * p.q.st + i * p.q.si + c, true);
+      stage_vec<E>(Qs + ir * kstr + c, gq + (int64_t)min(r0 + r, cnt - 1) * p.q.st + i * p.q.si + c, true);
     }
   }
   for (int i = 0; i < N; ++i) {
@@ -137,7 +157,7 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
 
   auto qrow = [&](int i) -> const E* {
     if constexpr (QLDS) return Qs + (i * 32 + c32) * kstr;
-    else return gq + (int64_t)min(r0 + c32, p.Tq - 1) * p.q.st + i * p.q.si;
+    else return gq + (int64_t)min(r0 + c32, cnt - 1) * p.q.st + i * p.q.si;
   };
   // S^T (keys x queries) of branch i against the staged K_i image, in log2 units;
   // masked: key kt*32 + rowof(r, hf) above this lane's query position -> -inf
@@ -253,14 +273,17 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
     }
   }
   // O^T: registers 4g..4g+3 of block d = columns 32d + 8g + 4hf .. +3 of query row c32
+  // (rows cnt .. Tq-1 of a ragged batch are padding: zeros)
   if (wave == 0 && r0 + c32 < p.Tq) {
     E* go = reinterpret_cast<E*>(p.o.p) + b * p.o.sb + (int64_t)(r0 + c32) * p.o.st + h * p.o.sh;
+    const bool real = r0 + c32 < cnt;
 #pragma unroll
     for (int d = 0; d < NDB; ++d)
       if (d < ndb)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          store4<E>(go + d * 32 + 8 * g + 4 * hf, acc[d][4 * g], acc[d][4 * g + 1], acc[d][4 * g + 2], acc[d][4 * g + 3]);
+          store4<E>(go + d * 32 + 8 * g + 4 * hf, real ? acc[d][4 * g] : 0.f, real ? acc[d][4 * g + 1] : 0.f,
+                    real ? acc[d][4 * g + 2] : 0.f, real ? acc[d][4 * g + 3] : 0.f);
   }
 }
 

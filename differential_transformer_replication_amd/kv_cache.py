@@ -28,11 +28,20 @@ a tool result, the scoring of candidate tokens with ``all_rows=True``), through
 ``ops.diff_attention_extend``, which writes nothing but its output.  The same step
 prefills a long prompt in bounded memory (``prefill_chunk``): the first chunk runs
 the fused training forward, every further chunk appends.
+
+Everything above keeps the whole batch at one position (``KVCache.length``).  The
+ragged path next to it (``RaggedKVCache``, ``prefill_ragged``, ``decode_ragged``,
+``append_ragged``, ``generate_ragged``) keeps one length per sequence on the device,
+read there by ``ops.diff_attention_decode_ragged`` / ``ops.diff_attention_extend_ragged``:
+prompts of different lengths generate as one batch, a verification step accepts a
+different number of tokens per sequence (``RaggedKVCache.truncate`` rolls the rest
+back), and a sequence may sit at position 0 while the others are far along.  It runs
+eagerly and within one window; no existing path enters it.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch.nn import functional as F
@@ -41,7 +50,8 @@ from . import ops
 from ._compat import mha_out_scale
 
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
-           "prefill_logits", "check_prefill_chunk"]
+           "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
+           "append_ragged", "generate_ragged"]
 
 
 def enabled(idx: torch.Tensor, model=None) -> bool:
@@ -329,3 +339,298 @@ def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk
         probs = F.softmax(logits, dim=-1)
         idx = torch.cat((idx, torch.multinomial(probs, num_samples=1)), dim=1)
     return idx
+
+
+# ---------------------------------------------------------------------- ragged ---
+class RaggedKVCache(KVCache):
+    """A ``KVCache`` whose sequences each sit at their own length.
+
+    The per-layer packed rows are the same ``(B, block_size, H*N*hs + H*dv)`` views
+    (``rows``); each is cut from a ``(B, block_size + 1, ...)`` allocation (``store``)
+    whose last row no kernel reads: the padding rows of a ragged step are written
+    there.  ``lengths`` is a device int32 ``(B,)`` the kernels read; ``host_lengths``
+    is the host's copy, kept in step by every function here.  Only ``decode_ragged``
+    with a device-side ``active`` mask (``generate_ragged`` with ``eos_id``) cannot keep
+    it exact without a sync: ``host_lengths`` is then an upper bound (``host_exact`` is
+    False) until ``sync()``."""
+
+    def __init__(self):
+        super().__init__()
+        self.use_graph = False                     # the ragged step runs eagerly
+        self.store: Dict[int, torch.Tensor] = {}
+        self.lengths: Optional[torch.Tensor] = None
+        self.host_lengths: List[int] = []
+        self.host_exact = True
+
+    def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
+        buf = self.store.get(layer)
+        if buf is None or buf.shape != (B, cap + 1, width) or buf.dtype != like.dtype:
+            buf = torch.empty(B, cap + 1, width, device=like.device, dtype=like.dtype)
+            self.store[layer] = buf
+            self.rows[layer] = buf[:, :cap]
+        return self.rows[layer]
+
+    def set_lengths(self, lengths: Sequence[int], device) -> None:
+        self.host_lengths = [int(n) for n in lengths]
+        self.lengths = torch.tensor(self.host_lengths, dtype=torch.int32, device=device)
+        self.host_exact = True
+
+    def sync(self) -> List[int]:
+        """Refresh ``host_lengths`` from the device (one host sync)."""
+        if self.lengths is not None:
+            self.host_lengths = self.lengths.tolist()
+        self.host_exact = True
+        return self.host_lengths
+
+    def truncate(self, new_lengths) -> None:
+        """Roll every sequence back to ``new_lengths[b] <= lengths[b]`` (the tokens a
+        verification step did not accept).  Nothing is erased: the kernels ignore rows
+        past a sequence's length, and the next step overwrites them."""
+        if self.lengths is None:
+            raise ValueError("truncate needs a prefilled cache")
+        new = [int(n) for n in (new_lengths.tolist() if isinstance(new_lengths, torch.Tensor) else new_lengths)]
+        if not self.host_exact:
+            self.sync()
+        if len(new) != len(self.host_lengths):
+            raise ValueError(f"{len(new)} lengths for a batch of {len(self.host_lengths)}")
+        for b, (n, have) in enumerate(zip(new, self.host_lengths)):
+            if not 0 <= n <= have:
+                raise ValueError(f"sequence {b}: cannot truncate length {have} to {n}")
+        self.set_lengths(new, self.lengths.device)
+
+
+def _ragged_attention_step(block, x, layer: int, cache: RaggedKVCache, pos, counts, rows, one_row: bool):
+    """``_attention_step`` for rows at per-sequence positions: sequence b's Tn rows sit
+    at pos[b] .. pos[b]+Tn-1, the first counts[b] of them real (pos, counts: device
+    int32 (B,); rows: their (B, Tn) long positions, clamped to the window).  The real
+    rows' K_i / V go to cache rows pos[b] + r, the padding rows' to the spare row."""
+    attn, H, N, hs, dv, bs = _spec(block)
+    consts = cache.consts.get(layer)
+    if consts is None:
+        consts = _constants(attn, layer, H, hs, bs, x.device)
+        cache.consts[layer] = consts
+    weight, coef, freqs = consts
+    qkv = F.linear(x, weight)
+    B, Tn, W = qkv.shape
+    nq = H * N * hs
+    buf = cache.layer(layer, B, bs, W - nq, qkv)
+    store = cache.store[layer]
+    q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
+    new_rows = qkv[..., nq:]
+    if freqs is not None:
+        # one table row per (b, r): the (B, Tn, ...) views collapse to (1, B*Tn, ...)
+        tab = freqs[rows.flatten()]
+        k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
+        q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+        k_rot = torch.empty_like(q_rot)
+        ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
+        ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
+        q = q_rot
+        new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
+    r = torch.arange(Tn, device=qkv.device)
+    real = r[None, :] < counts[:, None]
+    dst = torch.where(real, pos[:, None].long() + r[None, :], bs).clamp_(max=bs)
+    store.index_put_((torch.arange(B, device=qkv.device)[:, None].expand(B, Tn), dst), new_rows)
+    k_rows = buf[..., :nq].unflatten(-1, (H, N, hs))
+    v_rows = buf[..., nq:].unflatten(-1, (H, dv))
+    if one_row:
+        out = ops.diff_attention_decode_ragged(q[:, 0], k_rows, v_rows, coef, pos + counts).view(B, 1, H * dv)
+    elif ops.extend_supported(qkv.dtype, hs, N, dv):
+        out = ops.diff_attention_extend_ragged(q, k_rows, v_rows, coef, pos, counts)
+    else:
+        # no extend plan for this head size (as _extend_rows): one ragged decode per row,
+        # a padding row at length 0 (zeros)
+        zero = torch.zeros_like(pos)
+        out = torch.stack([ops.diff_attention_decode_ragged(q[:, i], k_rows, v_rows, coef,
+                                                            torch.where(counts > i, pos + (i + 1), zero))
+                           for i in range(Tn)], dim=1)
+    if hasattr(attn, "group_norm"):
+        gn = attn.group_norm
+        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
+    return attn.dropout(attn.proj(out))
+
+
+def _ragged_model_step(model, idx, cache: RaggedKVCache, pos, counts, gather=None, one_row: bool = False):
+    """The model's forward over (B, T) tokens, sequence b's at positions pos[b] ..
+    (``pos=None``: a right-padded prefill from position 0 through the fused training
+    forward).  Returns every row's logits (B, T, vocab), or with ``gather`` (long (B,))
+    row gather[b] of each sequence (B, vocab)."""
+    B, T = idx.shape
+    r = torch.arange(T, device=idx.device)
+    rows = r if pos is None else (pos[:, None].long() + r[None, :]).clamp_(max=model.block_size - 1)
+    x = model.token_embedding_table(idx)
+    if hasattr(model, "position_embedding_table"):
+        x = x + model.position_embedding_table(rows)
+    for layer, block in enumerate(model.blocks, 1):
+        h = block.ln1(x)
+        if pos is None:
+            x = x + _attention_step(block, h, layer, cache, 0)
+        else:
+            x = x + _ragged_attention_step(block, h, layer, cache, pos, counts, rows, one_row)
+        x = x + block.ffwd(block.ln2(x))
+    if gather is None:
+        return model.lm_head(model.ln_f(x))
+    x = x[torch.arange(B, device=idx.device), gather].unsqueeze(1)
+    return model.lm_head(model.ln_f(x))[:, 0]
+
+
+def _check_ragged(cache, B: int) -> None:
+    if not isinstance(cache, RaggedKVCache) or cache.lengths is None:
+        raise ValueError("a prefilled RaggedKVCache is needed: run prefill_ragged first")
+    if len(cache.host_lengths) != B:
+        raise ValueError(f"batch size {B} differs from the cache's {len(cache.host_lengths)}")
+
+
+@torch.no_grad()
+def prefill_ragged(model, prompts: Sequence[torch.Tensor], cache: RaggedKVCache) -> torch.Tensor:
+    """Prefill ``cache`` with B prompts of different lengths (one-dimensional
+    LongTensors, 1 .. block_size tokens each) in one fused forward: the prompts are
+    right-padded to the longest (the forward is causal, so the padding cannot reach a
+    real row), every row's K_i / V is cached and ``lengths[b] = len(prompts[b])`` hides
+    the padding.  Returns (B, vocab): each sequence's logits at its own last token."""
+    bs = model.block_size
+    lens = []
+    for p in prompts:
+        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.long:
+            raise ValueError("prompts must be one-dimensional LongTensors")
+        if not 1 <= p.shape[0] <= bs:
+            raise ValueError(f"a prompt of {p.shape[0]} tokens is outside 1 .. block_size {bs}")
+        lens.append(p.shape[0])
+    if not lens:
+        raise ValueError("no prompts")
+    if not isinstance(cache, RaggedKVCache):
+        raise ValueError("prefill_ragged needs a RaggedKVCache")
+    idx = torch.nn.utils.rnn.pad_sequence(list(prompts), batch_first=True)
+    last = torch.tensor(lens, device=idx.device) - 1
+    logits = _ragged_model_step(model, idx, cache, None, None, gather=last)
+    cache.set_lengths(lens, idx.device)
+    return logits
+
+
+@torch.no_grad()
+def decode_ragged(model, tok: torch.Tensor, cache: RaggedKVCache, active: Optional[torch.Tensor] = None):
+    """One new token per sequence: ``tok`` (B, 1) is sequence b's token at position
+    ``lengths[b]``.  Its K_i / V row is scattered there, the position-table or RoPE row
+    is gathered per sequence, and each layer runs one ``diff_attention_decode_ragged``
+    over ``lengths + 1``.  Returns (B, vocab) and advances every length by one.
+
+    ``active``: optional device bool (B,).  A sequence with ``active[b]`` False is
+    finished: its length stays, nothing of it is cached and its logits are unspecified.
+    The mask is applied on the device (no host sync), so ``host_lengths`` becomes an
+    upper bound (``RaggedKVCache.sync``)."""
+    if tok.dim() != 2 or tok.shape[1] != 1:
+        raise ValueError("tok must be (B, 1)")
+    B, bs = tok.shape[0], model.block_size
+    _check_ragged(cache, B)
+    if active is None:
+        if max(cache.host_lengths) + 1 > bs:
+            raise ValueError(f"a sequence is at block_size {bs}: positions are absolute within the window, "
+                             "the sliding window is the one-length path's job (last_logits)")
+        counts = torch.ones_like(cache.lengths)
+    else:
+        counts = active.to(torch.int32)
+    logits = _ragged_model_step(model, tok, cache, cache.lengths, counts, one_row=True)[:, 0]
+    cache.lengths = cache.lengths + counts
+    cache.host_lengths = [min(n + 1, bs) for n in cache.host_lengths]
+    if active is not None:
+        cache.host_exact = False
+    return logits
+
+
+@torch.no_grad()
+def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, all_rows: bool = False):
+    """Feed sequence b the first ``counts[b]`` tokens of ``new_idx[b]`` ((B, Tn), padded;
+    ``0 <= counts[b] <= Tn``) at positions ``lengths[b] ..``: one
+    ``diff_attention_extend_ragged`` per layer (head sizes without an extend plan: one
+    ragged decode per row).  Returns each sequence's logits at its last real row
+    (B, vocab), or with ``all_rows`` every row's (B, Tn, vocab), where row r < counts[b]
+    is the distribution after ``new_idx[b, r]`` -- the verification of speculated tokens;
+    ``cache.truncate`` then rolls back what was not accepted.  Padding rows, and the
+    returned row of a sequence with count 0 (whose length stays), are unspecified.
+
+    Raises ``ValueError`` if any ``lengths[b] + counts[b] > block_size``.  ``counts`` is
+    read on the host (a list, or a tensor: one sync).  A sequence so close to
+    block_size that its padded rows would not fit (``lengths[b] + Tn > block_size``) makes
+    the step run as several narrower ones."""
+    if new_idx.dim() != 2 or new_idx.shape[1] < 1:
+        raise ValueError("new_idx must be (B, Tn) with Tn >= 1")
+    B, Tn = new_idx.shape
+    bs = model.block_size
+    _check_ragged(cache, B)
+    if not cache.host_exact:
+        cache.sync()
+    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+    if len(cnt) != B:
+        raise ValueError(f"{len(cnt)} counts for a batch of {B}")
+    for b, (c, n) in enumerate(zip(cnt, cache.host_lengths)):
+        if not 0 <= c <= Tn:
+            raise ValueError(f"sequence {b}: count {c} outside 0 .. {Tn}")
+        if n + c > bs:
+            raise ValueError(f"sequence {b}: appending {c} tokens at length {n} crosses block_size {bs}")
+    dev = new_idx.device
+    cnt_dev = torch.tensor(cnt, dtype=torch.int32, device=dev)
+    out = None
+    done = 0
+    while done < Tn:
+        # the kernel needs pos[b] + width <= block_size of every sequence that still has real rows
+        live = [n + done for c, n in zip(cnt, cache.host_lengths) if c > done]
+        w = min(Tn - done, bs - max(live)) if live else min(Tn - done, bs)
+        pos = cache.lengths + cnt_dev.clamp(max=done)
+        part_cnt = (cnt_dev - done).clamp_(0, w)
+        part_idx = new_idx[:, done:done + w]
+        if all_rows:
+            part = _ragged_model_step(model, part_idx, cache, pos, part_cnt)
+            out = part if out is None else torch.cat([out, part], dim=1)
+        else:
+            last = (cnt_dev.long() - 1 - done).clamp_(0, w - 1)
+            part = _ragged_model_step(model, part_idx, cache, pos, part_cnt, gather=last)
+            here = ((cnt_dev > done) | (done == 0))[:, None]
+            out = part if out is None else torch.where(here, part, out)
+        done += w
+    cache.lengths = cache.lengths + cnt_dev
+    cache.host_lengths = [n + c for n, c in zip(cache.host_lengths, cnt)]
+    return out
+
+
+@torch.no_grad()
+def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None):
+    """``generate`` for B prompts of different lengths as one batch (any of the three
+    models): one ``prefill_ragged``, then one ``decode_ragged`` step per token.  Sampling
+    is the reference's (softmax of the last logits, ``torch.multinomial`` over the whole
+    batch, diff_transformer.py:177-185).  Returns a list of B one-dimensional tensors,
+    prompt b followed by its ``max_new_tokens`` samples; with ``eos_id`` a sequence ends
+    at its first sampled ``eos_id`` (kept): from then on its length is frozen and its
+    further samples are discarded.
+
+    Positions are absolute within the window, and a slide re-bases every cached
+    position: that stays the one-length path's job (``model.generate``).  So this
+    raises ``ValueError`` if any ``len(prompts[b]) + max_new_tokens > block_size``.  The
+    loop never reads a length back to the host; the one sync is at the end, where
+    ``eos_id`` cuts the outputs."""
+    bs = model.block_size
+    for p in prompts:
+        if p.shape[0] + max_new_tokens > bs:
+            raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
+                             f"block_size {bs}: the sliding window is the one-length path's job")
+    cache = RaggedKVCache()
+    logits = prefill_ragged(model, prompts, cache)
+    if max_new_tokens < 1:
+        return [p.clone() for p in prompts]
+    active = None if eos_id is None else torch.ones(len(prompts), dtype=torch.bool, device=logits.device)
+    new = []
+    for step in range(max_new_tokens):
+        probs = F.softmax(logits, dim=-1)
+        tok = torch.multinomial(probs, num_samples=1)
+        new.append(tok)
+        if step + 1 == max_new_tokens:
+            break
+        if active is not None:
+            active = active & (tok[:, 0] != eos_id)
+        logits = decode_ragged(model, tok, cache, active)
+    toks = torch.cat(new, dim=1)
+    keep = [max_new_tokens] * len(prompts)
+    if eos_id is not None:
+        hit = toks == eos_id
+        first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
+        keep = first.tolist()
+    return [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(prompts)]

@@ -769,3 +769,89 @@ def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
                         coef.data_ptr())
     _lib.check(lib.dta_attn_extend(a, _lib.stream_handle(q.device)))
     return o.view(B, Tq, H * dv)
+
+
+# ------------------------------------------------------------------ ragged ---
+def _batch_int32(t: Tensor, B: int, like: Tensor, name: str) -> None:
+    if not isinstance(t, Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != like.device:
+        raise RuntimeError(f"{name} must be a device int32 tensor of shape ({B},) on {like.device}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+
+
+def diff_attention_decode_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, lengths: Tensor,
+                                 max_length: Optional[int] = None) -> Tensor:
+    """``diff_attention_decode`` for a batch whose sequences sit at different lengths:
+    o[b] = sum_i coef[h,i] softmax(q_i[b] K_i[b, :len_b]^T / sqrt(hs)) V[b, :len_b], len_b = lengths[b].
+
+    q, k_cache, v_cache, coef as for ``diff_attention_decode``; ``lengths``: device int32
+    (B,), read by the kernels (no host sync).  ``max_length``: a host upper bound of every
+    length, which sizes the grid; default T_cap.  The kernels clamp each length to
+    [0, max_length]; a sequence of length 0 gets zeros; cache rows past a sequence's
+    length may hold anything.  With all lengths equal to L the result is bitwise that of
+    ``diff_attention_decode(..., L)``, whatever ``max_length``.  Returns (B, H*dv)."""
+    lib = _lib.load()
+    _require_gpu(q, k_cache, v_cache, coef)
+    B, H, N, hs = q.shape
+    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
+    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
+        raise RuntimeError("k_cache/v_cache shapes do not match q")
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
+        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+    _batch_int32(lengths, B, q, "lengths")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
+    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    a = _lib.DecodeRaggedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
+                              _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_cache), _lib.tensor5(v_cache),
+                              _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr())
+    _lib.check(lib.dta_attn_decode_ragged(a, _lib.stream_handle(q.device)))
+    return o.view(B, H * dv)
+
+
+def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: Tensor,
+                                 counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_extend`` for a batch whose sequences sit at different positions:
+    sequence b appends ``counts[b]`` real rows at absolute position ``pos[b]``; row r <
+    counts[b] is ``diff_attention_extend``'s row at pos = pos[b], rows r >= counts[b] are
+    zeros (padding; those q rows are never read).
+
+    q: (B, Tq, H, N, hs) padded; caches as for ``diff_attention_extend``, with rows
+    0 .. pos[b]+counts[b]-1 of sequence b valid and everything above arbitrary.  ``pos``,
+    ``counts``: device int32 (B,), read by the kernel (no host sync); ``counts=None``:
+    Tq for every sequence.  The kernel clamps pos[b] to [0, T_cap - Tq] and counts[b] to
+    [0, Tq].  With all pos equal and ``counts=None`` the result is bitwise that of
+    ``diff_attention_extend``.  Returns (B, Tq, H*dv).  No fallback: raises for a shape
+    without a kernel plan (``extend_supported``)."""
+    lib = _lib.load()
+    _require_gpu(q, k_cache, v_cache, coef)
+    if q.dim() != 5:
+        raise RuntimeError("q must be (B, Tq, H, N, hs)")
+    B, Tq, H, N, hs = q.shape
+    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
+    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
+        raise RuntimeError("k_cache/v_cache shapes do not match q")
+    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
+        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+    if tuple(coef.shape) != (H, N):
+        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+    _batch_int32(pos, B, q, "pos")
+    if counts is not None:
+        _batch_int32(counts, B, q, "counts")
+    if Tq > T_cap:
+        raise RuntimeError(f"{Tq} new rows do not fit the cache's {T_cap} rows")
+    if not extend_supported(q.dtype, hs, N, dv):
+        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
+    if B * Tq == 0:
+        return o.view(B, Tq, H * dv)
+    a = _lib.ExtendRaggedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, T_cap, 1.0 / math.sqrt(hs),
+                              _lib.tensor5(q), _lib.tensor5(k_cache), _lib.tensor5(v_cache), _lib.tensor5(o),
+                              coef.data_ptr(), pos.data_ptr(), None if counts is None else counts.data_ptr())
+    _lib.check(lib.dta_attn_extend_ragged(a, _lib.stream_handle(q.device)))
+    return o.view(B, Tq, H * dv)

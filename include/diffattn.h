@@ -44,6 +44,9 @@ extern "C" {
 #endif
 
 #define DTA_ABI_VERSION 9   /* 9: dta_attn_extend (several new rows over the KV cache), dta_extend_supported;
+                                  still 9, added without a bump (no existing struct or entry point changed):
+                                  dta_attn_decode_ragged, dta_attn_extend_ragged (per-sequence lengths) -- the
+                                  presence of the symbols is the capability check (dlsym / hasattr);
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -273,6 +276,36 @@ int dta_attn_decode(const dta_attn_decode_args* a, void* stream);
 size_t dta_attn_decode_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, int32_t head_size, int32_t dv,
                                        int32_t t_cap);
 
+/* dta_attn_decode for a ragged batch: every sequence of the batch at its own length.
+ * Replaces the same reference lines as dta_attn_decode (the per-token full-prefix
+ * recompute of generate(), diff_transformer.py:177-185; Ndiff_transformer.py generate;
+ * control.py:163-171) for B sequences whose prompts, accepted tokens or restarts left
+ * them at different positions: for every (b, h)
+ *   o[b] = sum_i coef[h][i] * softmax(q_i[b] . K_i[b][0:len_b]^T * scale) V[b][0:len_b]
+ * with len_b = lengths_dev[b], the number of valid cached keys of sequence b (its new
+ * token's own row included).  Everything else -- tensors, alignment, plans, workspace
+ * (dta_attn_decode_workspace_bytes), the chunk choice from t_cap only -- is
+ * dta_attn_decode's; `length` is the host upper bound of every len_b and sizes the
+ * grid (t_cap needs no host knowledge of the lengths).  Every kernel clamps len_b to
+ * [0, length].  len_b == 0 writes zeros (no NaN, no Inf).  Cache rows >= len_b of
+ * sequence b may hold anything, NaN included: they never reach the output, and a key
+ * chunk wholly past len_b exits before it touches memory, so the cache traffic of a
+ * call is sum_b len_b rows, not B * max.  With every len_b = L the output is bitwise
+ * equal to dta_attn_decode at length = L (same t_cap).  lengths_dev NULL or not
+ * 4-byte aligned: DTA_ERR_INVALID. */
+typedef struct dta_attn_decode_ragged_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t length;            /* host upper bound of every lengths_dev[b] (<= t_cap); sizes the grid */
+  int32_t t_cap;             /* workspace row length (>= length) */
+  float scale;
+  dta_tensor q, k_cache, v_cache, o;
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* lengths_dev;/* device int32 [B], required: valid cached keys of sequence b */
+} dta_attn_decode_ragged_args;
+int dta_attn_decode_ragged(const dta_attn_decode_ragged_args* a, void* stream);
+
 /* Several new rows over a KV cache (ABI 9): append to a live cache, scoring of
  * candidate tokens, chunked prefill.  Replaces DiffHead.forward's scores / mask /
  * softmax / combine / @V (diff_transformer.py:57-72; Ndiff_transformer.py:102-125)
@@ -305,6 +338,39 @@ typedef struct dta_attn_extend_args {
 } dta_attn_extend_args;
 int dta_attn_extend(const dta_attn_extend_args* a, void* stream);
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv);
+
+/* dta_attn_extend for a ragged batch (same reference lines: diff_transformer.py:57-72,
+ * Ndiff_transformer.py:102-125, for the newest rows only): sequence b appends count_b
+ * real rows at its own position pos_b -- the verification of speculated tokens (each
+ * sequence accepted a different number before), a second turn of different lengths, a
+ * fresh sequence (pos_b = 0) joining a live batch.  q and o hold Tq rows per sequence,
+ * padded; for row r of sequence b
+ *   r <  count_b:  o[b][r][h] = sum_i coef[h][i] * softmax_j(q_i[b][r][h] . K_i[b][j][h] * scale, j <= pos_b + r) V[b][j][h]
+ *                  (dta_attn_extend's formula with pos = pos_b)
+ *   r >= count_b:  o[b][r][h] = 0 (q rows count_b .. Tq-1 are never read)
+ * pos_dev: device int32 [B], required; count_dev: device int32 [B], or NULL = Tq for
+ * every sequence.  The kernel clamps pos_b to [0, t_cap - Tq] and count_b to [0, Tq],
+ * so no device value can index past the views.  Valid cache rows of sequence b are
+ * 0 .. pos_b + count_b - 1 (the caller writes the new rows' K_i / V first); every row
+ * above may hold anything, NaN included: it is never multiplied into the result.  A
+ * workgroup reads key tiles up to its own sequence's last needed one only, and a query
+ * tile without a real row writes its zeros and exits; count_b == 0 divides nothing.
+ * Shapes, alignment, plans and dta_extend_supported are dta_attn_extend's; with every
+ * pos_b = pos and count_dev NULL the output is bitwise equal to dta_attn_extend's.
+ * Tq > t_cap, a null pos_dev, a pointer not 4-byte aligned, a null tensor or a
+ * misaligned stride: DTA_ERR_INVALID.  Tq == 0 or B*H == 0: DTA_OK, no launch. */
+typedef struct dta_attn_extend_ragged_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded) */
+  int32_t t_cap;             /* rows of the cache views (>= Tq) */
+  float scale;
+  dta_tensor q, k_cache, v_cache, o;
+  const float* coef;         /* fp32 [h][i] */
+  const int32_t* pos_dev;    /* device int32 [B]: absolute position of query row 0 of sequence b */
+  const int32_t* count_dev;  /* device int32 [B] or NULL: real new rows of sequence b */
+} dta_attn_extend_ragged_args;
+int dta_attn_extend_ragged(const dta_attn_extend_ragged_args* a, void* stream);
 
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
