@@ -29,7 +29,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            "dta_accumulate_f32", "dta_swiglu_bwd_workspace_bytes", "dta_attn_bwd_dkdv_groups",
            "dta_attn_extend", "dta_extend_supported",
            # ragged batches, added within ABI 9: their presence is the capability check
-           "dta_attn_decode_ragged", "dta_attn_extend_ragged")
+           "dta_attn_decode_ragged", "dta_attn_extend_ragged",
+           # paged caches (block table over a pool of pages), added the same way
+           "dta_attn_decode_paged", "dta_attn_extend_paged")
 
 
 class DtaTensor(ctypes.Structure):
@@ -130,6 +132,26 @@ class ExtendRaggedArgs(ctypes.Structure):
                 ("coef", ctypes.c_void_p), ("pos_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p)]
 
 
+class DecodePagedArgs(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
+                ("length", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
+                ("q", DtaTensor), ("k_pool", DtaTensor), ("v_pool", DtaTensor), ("o", DtaTensor),
+                ("coef", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("lengths_dev", ctypes.c_void_p),
+                ("page_size", ctypes.c_int32), ("max_pages", ctypes.c_int32), ("n_pages", ctypes.c_int32),
+                ("block_table_dev", ctypes.c_void_p)]
+
+
+class ExtendPagedArgs(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
+                ("Tq", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
+                ("q", DtaTensor), ("k_pool", DtaTensor), ("v_pool", DtaTensor), ("o", DtaTensor),
+                ("coef", ctypes.c_void_p), ("pos_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p),
+                ("page_size", ctypes.c_int32), ("max_pages", ctypes.c_int32), ("n_pages", ctypes.c_int32),
+                ("block_table_dev", ctypes.c_void_p)]
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -163,6 +185,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.dta_extend_supported.argtypes = [ctypes.c_int32] * 4
         lib.dta_attn_decode_ragged.argtypes = [P(DecodeRaggedArgs), ctypes.c_void_p]
         lib.dta_attn_extend_ragged.argtypes = [P(ExtendRaggedArgs), ctypes.c_void_p]
+        lib.dta_attn_decode_paged.argtypes = [P(DecodePagedArgs), ctypes.c_void_p]
+        lib.dta_attn_extend_paged.argtypes = [P(ExtendPagedArgs), ctypes.c_void_p]
         lib.dta_attn_decode_workspace_bytes.restype = ctypes.c_size_t
         lib.dta_attn_bwd_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         lib.dta_attn_bwd_workspace_bytes.restype = ctypes.c_size_t
@@ -177,7 +201,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         for fn in ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_decode", "dta_ln_fwd", "dta_ln_bwd", "dta_rope", "dta_cast_f32",
                    "dta_abi_version", "dta_supported", "dta_swiglu_fwd", "dta_swiglu_bwd", "dta_accumulate_f32",
                    "dta_attn_bwd_dkdv_groups", "dta_attn_extend", "dta_extend_supported", "dta_attn_decode_ragged",
-                   "dta_attn_extend_ragged"):
+                   "dta_attn_extend_ragged", "dta_attn_decode_paged", "dta_attn_extend_paged"):
             getattr(lib, fn).restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")

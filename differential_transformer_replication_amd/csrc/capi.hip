@@ -486,19 +486,39 @@ size_t dta_attn_decode_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, in
 
 // dta_attn_decode and dta_attn_decode_ragged: one validation, one launch path.  ldev / lsb:
 // the device length(s) and their batch stride (0: one value, 1: int32 [B]).
+// The paged entry points' own arguments: a block table over a pool of n_pages pages of
+// page_size rows, max_pages entries per sequence, t_cap the logical capacity.
 extern "C++" template <class A>
-static int decode_call(const A* a, const int32_t* ldev, int lsb, void* stream) {
+static bool page_table(const A* a, PageTable& g) {
+  if (!a->block_table_dev || (uintptr_t)a->block_table_dev % 4) return false;
+  int shift = 0;
+  switch (a->page_size) {
+    case 32: shift = 5; break;
+    case 64: shift = 6; break;
+    case 128: shift = 7; break;
+    case 256: shift = 8; break;
+    default: return false;
+  }
+  if (a->n_pages < 1 || a->max_pages < 1 || (int64_t)a->max_pages * a->page_size != a->t_cap) return false;
+  g = PageTable{a->block_table_dev, a->max_pages, shift, a->n_pages};
+  return true;
+}
+
+// kc / vc: the cache views (contiguous [b][t], or with a table in pg the page pool)
+extern "C++" template <class A>
+static int decode_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const int32_t* ldev, int lsb,
+                       const PageTable& pg, void* stream) {
   if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (a->head_size % 8 || a->head_size > 128 || a->n_terms > 4 || a->dv > 256) return DTA_ERR_UNSUPPORTED;
   if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
   if ((int64_t)a->B * a->H == 0) return DTA_OK;
   // every operand is read or written by 16-byte vector accesses: full alignment checks on all four
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->k_cache, a->dtype, true) ||
-      !ok_tensor(a->v_cache, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef ||
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(kc, a->dtype, true) ||
+      !ok_tensor(vc, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef ||
       !aligned_ptr(a->workspace))
     return DTA_ERR_INVALID;
   DecodeParams p{};
-  p.q = t5(a->q); p.k = t5(a->k_cache); p.v = t5(a->v_cache); p.o = t5(a->o);
+  p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
   p.coef = a->coef; p.ws = a->workspace;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
   p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = ldev; p.Lsb = lsb;
@@ -509,12 +529,18 @@ static int decode_call(const A* a, const int32_t* ldev, int lsb, void* stream) {
 
 int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
   if (!a) return DTA_ERR_INVALID;
-  return decode_call(a, a->length_dev, 0, stream);
+  return decode_call(a, a->k_cache, a->v_cache, a->length_dev, 0, PageTable{}, stream);
 }
 
 int dta_attn_decode_ragged(const dta_attn_decode_ragged_args* a, void* stream) {
   if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4) return DTA_ERR_INVALID;
-  return decode_call(a, a->lengths_dev, 1, stream);
+  return decode_call(a, a->k_cache, a->v_cache, a->lengths_dev, 1, PageTable{}, stream);
+}
+
+int dta_attn_decode_paged(const dta_attn_decode_paged_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
+  return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream);
 }
 
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
@@ -523,17 +549,18 @@ int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int3
 
 // dta_attn_extend and dta_attn_extend_ragged: one validation, one launch path.
 extern "C++" template <class A>
-static int extend_call(const A* a, int pos, const int32_t* pos_dev, const int32_t* cnt_dev, void* stream) {
+static int extend_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, int pos, const int32_t* pos_dev,
+                       const int32_t* cnt_dev, const PageTable& pg, void* stream) {
   if (!ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (!extend_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
   if (pos < 0 || a->t_cap < 0 || (int64_t)pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
   if (a->Tq == 0 || (int64_t)a->B * a->H == 0) return DTA_OK;
   // every operand is read or written by 16-byte vector accesses (O by 8-byte ones)
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->k_cache, a->dtype, true) ||
-      !ok_tensor(a->v_cache, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef)
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(kc, a->dtype, true) ||
+      !ok_tensor(vc, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef)
     return DTA_ERR_INVALID;
   ExtendParams p{};
-  p.q = t5(a->q); p.k = t5(a->k_cache); p.v = t5(a->v_cache); p.o = t5(a->o);
+  p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
   p.coef = a->coef;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
   p.Tq = a->Tq; p.pos = pos; p.sl2 = a->scale * kLog2e;
@@ -543,12 +570,19 @@ static int extend_call(const A* a, int pos, const int32_t* pos_dev, const int32_
 
 int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
   if (!a) return DTA_ERR_INVALID;
-  return extend_call(a, a->pos, nullptr, nullptr, stream);
+  return extend_call(a, a->k_cache, a->v_cache, a->pos, nullptr, nullptr, PageTable{}, stream);
 }
 
 int dta_attn_extend_ragged(const dta_attn_extend_ragged_args* a, void* stream) {
   if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
-  return extend_call(a, 0, a->pos_dev, a->count_dev, stream);
+  return extend_call(a, a->k_cache, a->v_cache, 0, a->pos_dev, a->count_dev, PageTable{}, stream);
+}
+
+int dta_attn_extend_paged(const dta_attn_extend_paged_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4 || !page_table(a, pg))
+    return DTA_ERR_INVALID;
+  return extend_call(a, a->k_pool, a->v_pool, 0, a->pos_dev, a->count_dev, pg, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,11 @@
 // Algorithmic bytes per (b, h) and token: L * (N*hs + dv) * sizeof(E).
 // Ragged batches (dta_attn_decode_ragged) run the same kernels with L read per
 // sequence (clamp_len): L = len_b above, and a length of 0 writes zeros.
+// Paged caches (dta_attn_decode_paged) are the PG = true instantiations of the same
+// kernels: key row j of sequence b is row j % P of pool page table[b][j / P].  The
+// chunk is a whole number of pages, so the split kernel looks its (at most chunk / 32)
+// page ids up once, into LDS; every load, product and reduction after the address is
+// the unpaged kernel's, in the same order, so the outputs are bitwise equal.
 #include "dta_common.h"
 #include "dta_internal.h"
 
@@ -83,7 +88,14 @@ __device__ __forceinline__ int clamp_len(const DecodeParams& p, int b) {
   return p.Ldev ? min(max(p.Ldev[b * p.Lsb], 0), p.L) : p.L;
 }
 
-template <class E, int N>
+// element offset of cache row j of sequence b in the k / v view t (head and branch excluded)
+template <bool PG>
+__device__ __forceinline__ int64_t row_off(const DecodeParams& p, const T5& t, int b, int j) {
+  if constexpr (PG) return (int64_t)page_of(p.pg, b, j) * t.sb + (int64_t)(j & ((1 << p.pg.shift) - 1)) * t.st;
+  else return b * t.sb + (int64_t)j * t.st;
+}
+
+template <class E, int N, bool PG>
 __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   __shared__ float qs[N * 128];
   __shared__ float red[kWaves * N];
@@ -95,14 +107,14 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   __syncthreads();
 
   float* ws = p.ws + ((int64_t)b * p.H + h) * N * p.ldw;     // [i][ldw]
-  const E* gk = reinterpret_cast<const E*>(p.k.p) + b * p.k.sb + h * p.k.sh;
+  const E* gk = reinterpret_cast<const E*>(p.k.p) + h * p.k.sh;
   float m[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) m[i] = -INFINITY;
   for (int j = tid; j < L; j += kThreads) {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      const E* kr = gk + (int64_t)j * p.k.st + i * p.k.si;
+      const E* kr = gk + row_off<PG>(p, p.k, b, j) + i * p.k.si;
       float s = 0.f;
       for (int d = 0; d < HS; d += 8) {
         float f[8];
@@ -144,10 +156,10 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   // phase 4: G key groups x DV columns
   const int G = kThreads / DV;
   const int g = tid / DV, e = tid % DV;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + b * p.v.sb + h * p.v.sh + e;
+  const E* gv = reinterpret_cast<const E*>(p.v.p) + h * p.v.sh + e;
   float acc = 0.f;
   if (g < G)
-    for (int j = g; j < L; j += G) acc = fmaf(ws[j], (float)gv[(int64_t)j * p.v.st], acc);
+    for (int j = g; j < L; j += G) acc = fmaf(ws[j], (float)gv[row_off<PG>(p, p.v, b, j)], acc);
   part[tid] = acc;
   __syncthreads();
   if (tid < DV) {
@@ -170,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
 // halves the partials (A/B: +4.5% at B=8 H=16 L=32768, slower on smaller grids)
 constexpr int kWideGrid = 8192;
 
-template <class E, int N, int HS, int DV, int kChunk>
+template <class E, int N, int HS, int DV, int kChunk, bool PG>
 __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) {
   constexpr int LPR = HS / 8;                 // lanes per K row
   constexpr int KPW = 64 / LPR;               // keys per wave per load
@@ -181,12 +193,25 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   __shared__ float sc[N][kChunk];
   __shared__ float red[kWaves * N];
   __shared__ float part[G][N][DV + 4];
+  __shared__ int pgs[PG ? kChunk / 32 : 1];   // paged: the chunk's pool pages (page size >= 32)
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j0 = s * kChunk, L = clamp_len(p, b);
   if (j0 >= L) return;                         // grid sized for an upper bound; a chunk past its own
                                                // sequence's length touches no memory (uniform exit)
   const int nk = min(kChunk, L - j0);
+  // paged: the chunk starts on a page boundary (page size divides kChunk); only the pages
+  // that hold a row below L are looked up (the rest of the table may hold anything)
+  [[maybe_unused]] const int psh = p.pg.shift, pmask = (1 << psh) - 1;
+  if constexpr (PG) {
+    if (tid < kChunk / 32) pgs[tid] = (tid << psh) < nk ? page_of(p.pg, b, j0 + (tid << psh)) : 0;
+    __syncthreads();
+  }
+  // element offset of chunk row jj (< nk) in the view t
+  auto crow = [&](const T5& t, int jj) -> int64_t {
+    if constexpr (PG) return (int64_t)pgs[jj >> psh] * t.sb + (int64_t)(jj & pmask) * t.st;
+    else return b * t.sb + (int64_t)(j0 + jj) * t.st;
+  };
 
   // phase 1: scores of this chunk into LDS
   {
@@ -199,10 +224,10 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
 #pragma unroll
       for (int u = 0; u < 8; ++u) q[i][u] *= p.scale;
     }
-    const E* gk = reinterpret_cast<const E*>(p.k.p) + b * p.k.sb + h * p.k.sh + sub * 8;
+    const E* gk = reinterpret_cast<const E*>(p.k.p) + h * p.k.sh + sub * 8;
     for (int jj = wave * KPW + kr; jj < kChunk; jj += kWaves * KPW) {
       const bool ok = jj < nk;
-      const E* kp = gk + (int64_t)(j0 + (ok ? jj : 0)) * p.k.st;
+      const E* kp = gk + crow(p.k, ok ? jj : 0);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         float f[8];
@@ -242,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
 
   // phase 3: acc_i = sum_j e_ij V_j (thread = 8 columns of one row group)
   const int g = tid / VPR, c0 = (tid % VPR) * 8;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + b * p.v.sb + h * p.v.sh + c0;
+  const E* gv = reinterpret_cast<const E*>(p.v.p) + h * p.v.sh + c0;
   float acc[N][8];
 #pragma unroll
   for (int i = 0; i < N; ++i)
@@ -250,7 +275,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     for (int u = 0; u < 8; ++u) acc[i][u] = 0.f;
   for (int jj = g; jj < nk; jj += G) {
     float f[8];
-    ld8f<E, DTA_DEC_NT>(gv + (int64_t)(j0 + jj) * p.v.st, f);
+    ld8f<E, DTA_DEC_NT>(gv + crow(p.v, jj), f);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const float e = sc[i][jj];
@@ -324,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
 // current length, so the eager path (length = pos + 1) and the graph path
 // (length = t_cap, device length) launch the same chunks and reduce in the same
 // order: their outputs are bitwise equal at every position.
-template <class E, int N, int HS, int DV>
+template <class E, int N, int HS, int DV, bool PG>
 int split_launch(const DecodeParams& p0, hipStream_t st) {
   constexpr int C = DTA_DECODE_CHUNK;
   const int64_t s_cap = (p0.ldw + C - 1) / C;
@@ -335,43 +360,43 @@ int split_launch(const DecodeParams& p0, hipStream_t st) {
   DecodeParams p = p0;
   p.S = (p0.L + chunk - 1) / chunk;            // same partial layout as C-key chunks, fewer rows used
   if (wide) {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * C, PG>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
     hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * C>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
   } else {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, C, PG>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
     hipLaunchKernelGGL((decode_combine_kernel<E, N, C>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
   }
   return (int)hipGetLastError();
 }
 
-template <class E, int N>
+template <class E, int N, bool PG>
 int split_dispatch(const DecodeParams& p, hipStream_t st) {
-  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64>(p, st);
-  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128>(p, st);
-  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256>(p, st);
-  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64>(p, st);
-  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128>(p, st);
+  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64, PG>(p, st);
+  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128, PG>(p, st);
+  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256, PG>(p, st);
+  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64, PG>(p, st);
+  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128, PG>(p, st);
   return 1;    // no split plan: caller uses the single-pass kernel
 }
 
-template <class E>
+template <class E, bool PG>
 int decode_launch(const DecodeParams& p, hipStream_t st) {
   if (p.ml) {
     int e = 1;
     switch (p.N) {
-      case 1: e = split_dispatch<E, 1>(p, st); break;
-      case 2: e = split_dispatch<E, 2>(p, st); break;
-      case 3: e = split_dispatch<E, 3>(p, st); break;
-      case 4: e = split_dispatch<E, 4>(p, st); break;
+      case 1: e = split_dispatch<E, 1, PG>(p, st); break;
+      case 2: e = split_dispatch<E, 2, PG>(p, st); break;
+      case 3: e = split_dispatch<E, 3, PG>(p, st); break;
+      case 4: e = split_dispatch<E, 4, PG>(p, st); break;
     }
     if (e != 1) return e;
   }
   dim3 g(p.H, p.B);
   switch (p.N) {
-    case 1: hipLaunchKernelGGL((decode_kernel<E, 1>), g, dim3(kThreads), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((decode_kernel<E, 2>), g, dim3(kThreads), 0, st, p); break;
-    case 3: hipLaunchKernelGGL((decode_kernel<E, 3>), g, dim3(kThreads), 0, st, p); break;
-    case 4: hipLaunchKernelGGL((decode_kernel<E, 4>), g, dim3(kThreads), 0, st, p); break;
+    case 1: hipLaunchKernelGGL((decode_kernel<E, 1, PG>), g, dim3(kThreads), 0, st, p); break;
+    case 2: hipLaunchKernelGGL((decode_kernel<E, 2, PG>), g, dim3(kThreads), 0, st, p); break;
+    case 3: hipLaunchKernelGGL((decode_kernel<E, 3, PG>), g, dim3(kThreads), 0, st, p); break;
+    case 4: hipLaunchKernelGGL((decode_kernel<E, 4, PG>), g, dim3(kThreads), 0, st, p); break;
     default: return -2;
   }
   return (int)hipGetLastError();
@@ -382,9 +407,9 @@ int decode_launch(const DecodeParams& p, hipStream_t st) {
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st) {
   if ((int64_t)p.B * p.H == 0) return 0;
   switch (dtype) {
-    case 0: return decode_launch<__bf16>(p, st);
-    case 1: return decode_launch<_Float16>(p, st);
-    case 2: return decode_launch<float>(p, st);
+    case 0: return p.pg.tbl ? decode_launch<__bf16, true>(p, st) : decode_launch<__bf16, false>(p, st);
+    case 1: return p.pg.tbl ? decode_launch<_Float16, true>(p, st) : decode_launch<_Float16, false>(p, st);
+    case 2: return p.pg.tbl ? decode_launch<float, true>(p, st) : decode_launch<float, false>(p, st);
   }
   return -2;
 }

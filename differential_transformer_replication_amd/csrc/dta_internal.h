@@ -109,6 +109,22 @@ struct RopeParams {
 #define DTA_DECODE_CHUNK 256   // keys per workgroup of the split-key decode plan
 #endif
 
+// Paged caches (dta_attn_decode_paged / dta_attn_extend_paged): k / v describe a pool of
+// pages ([page][row < 2^shift][h][i]: sb = page stride, st = row stride) and row j of
+// sequence b lives at pool[tbl[b * max_pages + (j >> shift)]][j & (2^shift - 1)].
+// tbl == NULL: the contiguous cache ([b][t][h][i]) of every other entry point.
+struct PageTable {
+  const int* tbl;      // device int32 [B][max_pages]
+  int max_pages;       // table row length
+  int shift;           // log2(page size): 5 .. 8
+  int n_pages;         // pages of the pool: every id read from tbl is clamped to [0, n_pages - 1]
+};
+// the pool page that holds row j of sequence b, clamped so that no device value can index
+// outside the pool (as clamp_len and the pos_b clamp do for lengths and positions)
+__device__ __forceinline__ int page_of(const PageTable& g, int b, int j) {
+  return min(max(g.tbl[(int64_t)b * g.max_pages + (j >> g.shift)], 0), g.n_pages - 1);
+}
+
 struct DecodeParams {
   T5 q, k, v, o;       // q/o: one row per (b, h) (st unused); k/v: the cache [b][t][h][i]
   const float* coef;   // [h][i]
@@ -118,6 +134,7 @@ struct DecodeParams {
   float scale;
   const int* Ldev;     // optional device length
   int Lsb;             // batch stride of Ldev: 0 = one length for the launch, 1 = int32 [B] (ragged)
+  PageTable pg;        // paged launch: k / v are the page pool, ldw = max_pages * page size
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
@@ -131,7 +148,8 @@ struct ExtendParams {
   // ragged batches (dta_attn_extend_ragged; both NULL = the one-position launch above)
   const int* pos_dev;  // int32 [B]: sequence b's pos, clamped to [0, cap - Tq]
   const int* cnt_dev;  // optional int32 [B]: real rows of sequence b, clamped to [0, Tq]; rows past it are written as zeros
-  int cap;             // rows of the cache views (the clamp of pos_dev)
+  int cap;             // rows of the cache views (the clamp of pos_dev); paged: max_pages * page size
+  PageTable pg;        // paged launch: k / v are the page pool
 };
 
 int launch_extend(int dtype, const ExtendParams& p, hipStream_t st);   // extend.hip

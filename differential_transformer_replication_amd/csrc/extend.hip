@@ -30,6 +30,12 @@
 // a real row exits after writing them.  The one-position launch is pos_b = pos,
 // count_b = Tq: the same instructions on the same values, so equal bit for bit.
 //
+// Paged caches (dta_attn_extend_paged) are the PG = true instantiations: the 32 rows of
+// key tile kt are rows (kt * 32) % P .. + 31 of pool page table[b][kt * 32 / P] (the page
+// size P is a multiple of 32, so a tile never straddles a page).  A wave looks the page
+// up once per tile, and only for tiles below its sequence's last needed one; everything
+// after the address is the unpaged kernel's, so the outputs are bitwise equal.
+//
 // The cache tail (rows >= pos + Tq) may hold anything, NaN included: those K and V
 // rows are staged as zeros (a masked probability of 0 times a NaN V row inside an
 // MFMA would still be NaN), and the per-element mask j <= pos + r uses absolute
@@ -97,7 +103,7 @@ __device__ __forceinline__ void stage_rows(E* img, int stride, const E* src, int
   }
 }
 
-template <class E, int NDB, bool QLDS>
+template <class E, int NDB, bool QLDS, bool PG>
 __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_off, int q_off, int tile_bytes) {
   using O = Ops<E>;
   using frag = typename O::frag;
@@ -136,8 +142,15 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   E* Qs = reinterpret_cast<E*>(smem + q_off);
 
   const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh;
-  const E* gk = reinterpret_cast<const E*>(p.k.p) + b * p.k.sb + h * p.k.sh;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + b * p.v.sb + h * p.v.sh;
+  const E* gk = reinterpret_cast<const E*>(p.k.p) + (PG ? 0 : b * p.k.sb) + h * p.k.sh;
+  const E* gv = reinterpret_cast<const E*>(p.v.p) + (PG ? 0 : b * p.v.sb) + h * p.v.sh;
+  // paged: key tile kt lies in pool page tile_page(kt) (view base + page * sb); stage_rows then
+  // counts rows from jt, the tile's first row inside its page, with the limit L moved along
+  [[maybe_unused]] const int pmask = (1 << p.pg.shift) - 1;
+  auto tile_page = [&](int kt) -> int64_t {
+    if constexpr (PG) return page_of(p.pg, b, kt * 32);
+    else return 0;
+  };
 
   // rows past the real ones of a partial query tile read the last real row (their result is never stored)
   if constexpr (QLDS) {
@@ -179,9 +192,11 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   // ---- pass 1: running (m_i, l_i) of this wave's key tiles
   for (int kt = wave; kt < ntiles; kt += nw) {
     const bool masked = kt * 32 + 31 > q0;
+    const int64_t pg = tile_page(kt);
+    const int jt = PG ? (kt * 32) & pmask : kt * 32, Lt = PG ? L - kt * 32 + jt : L;
     for (int i = 0; i < N; ++i) {
       wave_sync();                                 // the previous image's reads are done
-      stage_rows<E>(Kw, kstr, gk + i * p.k.si, p.k.st, HS, kt * 32, L, lane);
+      stage_rows<E>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane);
       wave_sync();
       const f32x16 sa = scores(i, kt, masked);
       float mt = -INFINITY;
@@ -223,12 +238,14 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   for (int d = 0; d < NDB; ++d) acc[d] = f32x16{};
   for (int kt = wave; kt < ntiles; kt += nw) {
     const bool masked = kt * 32 + 31 > q0;
+    const int64_t pg = tile_page(kt);
+    const int jt = PG ? (kt * 32) & pmask : kt * 32, Lt = PG ? L - kt * 32 + jt : L;
     wave_sync();
-    stage_rows<E>(Vw, vstr, gv, p.v.st, DV, kt * 32, L, lane);
+    stage_rows<E>(Vw, vstr, gv + pg * p.v.sb, p.v.st, DV, jt, Lt, lane);
     f32x16 pt = {};
     for (int i = 0; i < N; ++i) {
       wave_sync();
-      stage_rows<E>(Kw, kstr, gk + i * p.k.si, p.k.st, HS, kt * 32, L, lane);
+      stage_rows<E>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane);
       wave_sync();
       const f32x16 sa = scores(i, kt, masked);
       const float mi = fin[i * 64 + c32], ci = fin[i * 64 + 32 + c32];
@@ -287,9 +304,9 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   }
 }
 
-template <class E, int NDB, bool QLDS>
+template <class E, int NDB, bool QLDS, bool PG>
 int extend_go(const ExtendParams& p, const ExtendPlan& pl, hipStream_t st) {
-  auto kern = extend_kernel<E, NDB, QLDS>;
+  auto kern = extend_kernel<E, NDB, QLDS, PG>;
   // more than the default dynamic LDS limit: raised once per instantiation
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -299,19 +316,19 @@ int extend_go(const ExtendParams& p, const ExtendPlan& pl, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-template <class E>
+template <class E, bool PG>
 int extend_launch(const ExtendParams& p, hipStream_t st) {
   ExtendPlan pl;
   if (!extend_plan<E>(p.N, p.HS, p.DV, pl)) return -2;
   const int ndb = p.DV / 32;
   if (pl.qlds) {
-    if (ndb <= 2) return extend_go<E, 2, true>(p, pl, st);
-    if (ndb <= 4) return extend_go<E, 4, true>(p, pl, st);
-    return extend_go<E, 8, true>(p, pl, st);
+    if (ndb <= 2) return extend_go<E, 2, true, PG>(p, pl, st);
+    if (ndb <= 4) return extend_go<E, 4, true, PG>(p, pl, st);
+    return extend_go<E, 8, true, PG>(p, pl, st);
   }
-  if (ndb <= 2) return extend_go<E, 2, false>(p, pl, st);
-  if (ndb <= 4) return extend_go<E, 4, false>(p, pl, st);
-  return extend_go<E, 8, false>(p, pl, st);
+  if (ndb <= 2) return extend_go<E, 2, false, PG>(p, pl, st);
+  if (ndb <= 4) return extend_go<E, 4, false, PG>(p, pl, st);
+  return extend_go<E, 8, false, PG>(p, pl, st);
 }
 
 }  // namespace
@@ -327,9 +344,9 @@ int launch_extend(int dtype, const ExtendParams& p, hipStream_t st) {
   if ((int64_t)p.B * p.H * p.Tq == 0) return 0;
   if (!extend_supported(dtype, p.HS, p.N, p.DV)) return -2;
   switch (dtype) {
-    case 0: return extend_launch<__bf16>(p, st);
-    case 1: return extend_launch<_Float16>(p, st);
-    case 2: return extend_launch<float>(p, st);
+    case 0: return p.pg.tbl ? extend_launch<__bf16, true>(p, st) : extend_launch<__bf16, false>(p, st);
+    case 1: return p.pg.tbl ? extend_launch<_Float16, true>(p, st) : extend_launch<_Float16, false>(p, st);
+    case 2: return p.pg.tbl ? extend_launch<float, true>(p, st) : extend_launch<float, false>(p, st);
   }
   return -2;
 }

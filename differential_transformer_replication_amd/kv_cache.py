@@ -37,6 +37,15 @@ prompts of different lengths generate as one batch, a verification step accepts 
 different number of tokens per sequence (``RaggedKVCache.truncate`` rolls the rest
 back), and a sequence may sit at position 0 while the others are far along.  It runs
 eagerly and within one window; no existing path enters it.
+
+The paged path (``PagedKVCache``, ``prefill_paged``, ``decode_paged``, ``append_paged``,
+``generate_paged``) stores the same rows in a shared pool of fixed-size pages, reached by
+the kernels through a per-sequence block table (``ops.diff_attention_decode_paged`` /
+``ops.diff_attention_extend_paged``): a batch holds the pages its lengths need, not
+B x block_size rows; ``release`` hands a finished sequence's pages to the next prompt,
+which ``prefill_paged`` adds to the live cache; ``fork`` lets several continuations of
+one prompt share its pages (copy on write).  The allocator lives on the host; the step
+is eager, stays within one window, and no existing path enters it.
 """
 from __future__ import annotations
 
@@ -51,7 +60,8 @@ from ._compat import mha_out_scale
 
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
-           "append_ragged", "generate_ragged"]
+           "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
+           "append_paged", "generate_paged"]
 
 
 def enabled(idx: torch.Tensor, model=None) -> bool:
@@ -634,3 +644,503 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
         keep = first.tolist()
     return [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(prompts)]
+
+
+# ----------------------------------------------------------------------- paged ---
+class OutOfPages(RuntimeError):
+    """The pool has fewer free pages than a step needs.  Raised before anything is
+    written: the allocator, the tables and the lengths are as they were."""
+
+
+class PagedKVCache(KVCache):
+    """K_i / V rows of many sequences in one pool of ``num_pages`` pages of ``page_size``
+    rows (32, 64, 128 or 256), reached through a block table.
+
+    Per layer one ``(num_pages + 1, page_size, H*N*hs + H*dv)`` allocation (``pool``), made
+    on first use; the last page is a spare no table points to, where the padding rows of
+    a step are scattered (the ragged cache's spare row).  A sequence is named by the id
+    ``prefill_paged`` or ``fork`` returned; ids are never reused.  The host keeps the free
+    list, one refcount per page, each sequence's page list (``pages``) and length
+    (``host_lengths``); the device keeps ``block_table`` int32 ``(max_seqs, max_pages)``
+    (``max_pages = ceil(block_size / page_size)``, unused entries -1) and ``lengths`` int32
+    ``(max_seqs,)``, one row per live sequence (``slot``).  A step gathers the rows of its
+    sequences with ``index_select`` into the contiguous table the kernels take and
+    scatters the new lengths back.  Host changes of a table row or a length (prefill,
+    fork, copy on write, truncate, release) reach the device in one copy at the start of
+    the next step.
+
+    As for ``RaggedKVCache``, a ``decode_paged`` with a device-side ``active`` mask leaves
+    ``host_lengths`` an upper bound (``host_exact`` False) until ``sync()``; pages are then
+    taken for the bound and ``sync()`` / ``release`` return the surplus."""
+
+    def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None):
+        super().__init__()
+        if page_size not in ops.PAGE_SIZES:
+            raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
+        if num_pages < 1:
+            raise ValueError("num_pages must be >= 1")
+        self.use_graph = False                     # the paged step runs eagerly
+        self.num_pages, self.page_size = int(num_pages), int(page_size)
+        self.max_seqs = int(num_pages if max_seqs is None else max_seqs)
+        if self.max_seqs < 1:
+            raise ValueError("max_seqs must be >= 1")
+        self.pool: Dict[int, torch.Tensor] = {}
+        self.free: List[int] = list(range(self.num_pages - 1, -1, -1))    # a stack: pop() takes page 0 first
+        self.refcount: List[int] = [0] * self.num_pages
+        self.pages: Dict[int, List[int]] = {}
+        self.host_lengths: Dict[int, int] = {}
+        self.host_low: Dict[int, int] = {}         # the exact length at the last sync (<= the true length)
+        self.host_exact = True
+        self.slot: Dict[int, int] = {}
+        self.free_slots: List[int] = list(range(self.max_seqs - 1, -1, -1))
+        self.next_id = 0
+        self.max_pages = 0
+        self.block_table: Optional[torch.Tensor] = None
+        self.lengths: Optional[torch.Tensor] = None
+        self._dirty_rows: set = set()              # sequences whose table row / length the device has not seen
+        self._dirty_lens: set = set()
+
+    # ---- storage
+    def layer_pool(self, layer: int, width: int, like: torch.Tensor) -> torch.Tensor:
+        buf = self.pool.get(layer)
+        shape = (self.num_pages + 1, self.page_size, width)
+        if buf is None or buf.shape != shape or buf.dtype != like.dtype:
+            buf = torch.empty(shape, device=like.device, dtype=like.dtype)
+            self.pool[layer] = buf
+        return buf
+
+    def _ensure(self, block_size: int, device) -> None:
+        if self.block_table is None:
+            self.max_pages = -(-block_size // self.page_size)
+            self.block_table = torch.full((self.max_seqs, self.max_pages), -1, dtype=torch.int32, device=device)
+            self.lengths = torch.zeros(self.max_seqs, dtype=torch.int32, device=device)
+
+    def pages_in_use(self) -> int:
+        return self.num_pages - len(self.free)
+
+    # ---- host allocator
+    def _need(self, n: int) -> int:
+        return -(-n // self.page_size)
+
+    def _drop(self, page: int) -> None:
+        self.refcount[page] -= 1
+        if self.refcount[page] == 0:
+            self.free.append(page)
+
+    def _check_live(self, seqs: Sequence[int]) -> List[int]:
+        seqs = [int(q) for q in seqs]
+        if self.block_table is None:
+            raise ValueError("a prefilled PagedKVCache is needed: run prefill_paged first")
+        for q in seqs:
+            if q not in self.slot:
+                raise ValueError(f"sequence {q} is not live in this cache (never made, or released)")
+        if len(set(seqs)) != len(seqs):
+            raise ValueError("a sequence is named twice")
+        return seqs
+
+    def _plan_writes(self, seqs: Sequence[int], upto: Sequence[int]):
+        """What sequence q needs before it writes rows below ``upto[q]``: fresh pages past
+        its list and a copy of every page it shares (refcount > 1) from the page of its
+        lowest possible write position on.  Returns (copies [(seq, index)], grow [(seq, n)],
+        pages needed); changes nothing."""
+        rc: Dict[int, int] = {}
+        copies, grow, need = [], [], 0
+        for q, end in zip(seqs, upto):
+            have = self.pages[q]
+            for i in range(self.host_low[q] // self.page_size, min(self._need(end), len(have))):
+                pg = have[i]
+                if rc.get(pg, self.refcount[pg]) > 1:
+                    rc[pg] = rc.get(pg, self.refcount[pg]) - 1
+                    copies.append((q, i))
+                    need += 1
+            more = self._need(end) - len(have)
+            if more > 0:
+                grow.append((q, more))
+                need += more
+        return copies, grow, need
+
+    def _prepare_writes(self, seqs: Sequence[int], upto: Sequence[int]) -> None:
+        """Take the pages ``_plan_writes`` asks for (``OutOfPages`` first, if they are not
+        there), copy the shared ones on the device in every layer and repoint the tables."""
+        copies, grow, need = self._plan_writes(seqs, upto)
+        if need > len(self.free):
+            raise OutOfPages(f"{need} pages needed, {len(self.free)} of {self.num_pages} free")
+        src, dst = [], []
+        for q, i in copies:
+            old, new = self.pages[q][i], self.free.pop()
+            self.refcount[new] = 1
+            self._drop(old)
+            self.pages[q][i] = new
+            src.append(old)
+            dst.append(new)
+            self._dirty_rows.add(q)
+        for q, more in grow:
+            for _ in range(more):
+                new = self.free.pop()
+                self.refcount[new] = 1
+                self.pages[q].append(new)
+            self._dirty_rows.add(q)
+        if src:
+            for buf in self.pool.values():
+                buf.index_copy_(0, torch.tensor(dst, device=buf.device),
+                                buf.index_select(0, torch.tensor(src, device=buf.device)))
+
+    def _flush(self) -> None:
+        dev = self.block_table.device
+        rows = [q for q in self._dirty_rows if q in self.slot]
+        if rows:
+            tab = [self.pages[q] + [-1] * (self.max_pages - len(self.pages[q])) for q in rows]
+            self.block_table.index_copy_(0, torch.tensor([self.slot[q] for q in rows], device=dev),
+                                         torch.tensor(tab, dtype=torch.int32, device=dev).view(-1, self.max_pages))
+        lens = [q for q in self._dirty_lens if q in self.slot]
+        if lens:
+            self.lengths.index_copy_(0, torch.tensor([self.slot[q] for q in lens], device=dev),
+                                     torch.tensor([self.host_lengths[q] for q in lens], dtype=torch.int32, device=dev))
+        self._dirty_rows.clear()
+        self._dirty_lens.clear()
+
+    def _trim(self, q: int) -> None:
+        """Return the whole pages past sequence q's (exact) length."""
+        keep = self._need(self.host_lengths[q])
+        if len(self.pages[q]) > keep:
+            for pg in reversed(self.pages[q][keep:]):
+                self._drop(pg)
+            del self.pages[q][keep:]
+            self._dirty_rows.add(q)
+
+    def _new_seq(self, pages: List[int], length: int) -> int:
+        q = self.next_id
+        self.next_id += 1
+        self.slot[q] = self.free_slots.pop()
+        self.pages[q] = pages
+        self.host_lengths[q] = self.host_low[q] = length
+        self._dirty_rows.add(q)
+        self._dirty_lens.add(q)
+        return q
+
+    # ---- public
+    def sync(self) -> Dict[int, int]:
+        """Refresh ``host_lengths`` from the device (one host sync) and return the pages
+        that were taken for the upper bound only."""
+        if self.block_table is not None and not self.host_exact:
+            self._flush()
+            dev = self.lengths.tolist()
+            for q, sl in self.slot.items():
+                self.host_lengths[q] = self.host_low[q] = dev[sl]
+                self._trim(q)
+        self.host_exact = True
+        return self.host_lengths
+
+    def release(self, seq: int) -> None:
+        """Forget sequence ``seq``: every page of its list loses one reference, and the
+        pages nobody else holds go back to the free list."""
+        seq = int(seq)
+        if seq not in self.slot:
+            raise ValueError(f"sequence {seq} is not live in this cache (never made, or released twice)")
+        for pg in reversed(self.pages.pop(seq)):
+            self._drop(pg)
+        self.free_slots.append(self.slot.pop(seq))
+        del self.host_lengths[seq], self.host_low[seq]
+
+    def truncate(self, seq: int, new_length: int) -> None:
+        """Roll ``seq`` back to ``new_length <= its length`` and return the whole pages
+        past it.  Nothing is erased: the kernels ignore rows past a length."""
+        (seq,) = self._check_live([seq])
+        self.sync()
+        new_length = int(new_length)
+        if not 0 <= new_length <= self.host_lengths[seq]:
+            raise ValueError(f"sequence {seq}: cannot truncate length {self.host_lengths[seq]} to {new_length}")
+        self.host_lengths[seq] = self.host_low[seq] = new_length
+        self._dirty_lens.add(seq)
+        self._trim(seq)
+
+    def fork(self, seq: int) -> int:
+        """A new sequence with the same content as ``seq``, sharing every one of its
+        pages, a partial last page included (each refcount goes up by one; no device
+        work).  Whichever of them first writes into a shared page takes a fresh page and
+        copies the shared one there (copy on write, done by the next step)."""
+        (seq,) = self._check_live([seq])
+        self.sync()
+        if not self.free_slots:
+            raise RuntimeError(f"all {self.max_seqs} sequence slots are live (max_seqs)")
+        for pg in self.pages[seq]:
+            self.refcount[pg] += 1
+        return self._new_seq(list(self.pages[seq]), self.host_lengths[seq])
+
+
+def _paged_attention_step(block, x, layer: int, cache: PagedKVCache, tbl, pos, counts, rows, one_row: bool):
+    """``_ragged_attention_step`` over the page pool: ``tbl`` is the step's contiguous
+    (B, max_pages) table.  The real rows' K_i / V are scattered to row (pos[b] + r) % P of
+    page tbl[b, (pos[b] + r) // P], the padding rows' to the spare page, by one
+    ``index_put_``.  ``pos=None``: the right-padded prefill from position 0 (fused
+    training forward; counts = the prompt lengths)."""
+    attn, H, N, hs, dv, bs = _spec(block)
+    consts = cache.consts.get(layer)
+    if consts is None:
+        consts = _constants(attn, layer, H, hs, bs, x.device)
+        cache.consts[layer] = consts
+    weight, coef, freqs = consts
+    qkv = F.linear(x, weight)
+    B, Tn, W = qkv.shape
+    nq = H * N * hs
+    P, npg = cache.page_size, cache.num_pages
+    pool = cache.layer_pool(layer, W - nq, qkv)
+    r = torch.arange(Tn, device=qkv.device)
+    new_rows = qkv[..., nq:]
+    if pos is None:
+        out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
+        if freqs is not None:
+            k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+            ops.rope_rows(qkv[..., nq:2 * nq].unflatten(-1, (H, N, hs)), k_rot, freqs[:Tn])
+            new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
+        at = r[None, :].expand(B, Tn)
+    else:
+        q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
+        if freqs is not None:
+            tab = freqs[rows.flatten()]
+            k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
+            q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+            k_rot = torch.empty_like(q_rot)
+            ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
+            ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
+            q = q_rot
+            new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
+        at = pos[:, None].long() + r[None, :]
+    real = (r[None, :] < counts[:, None]) & (at < bs)
+    page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
+    pool.index_put_((page, at % P), new_rows)
+    if pos is not None:
+        k_pool = pool[:npg, :, :nq].unflatten(-1, (H, N, hs))
+        v_pool = pool[:npg, :, nq:].unflatten(-1, (H, dv))
+        if one_row:
+            out = ops.diff_attention_decode_paged(q[:, 0], k_pool, v_pool, coef, tbl, pos + counts).view(B, 1, H * dv)
+        elif ops.extend_supported(qkv.dtype, hs, N, dv):
+            out = ops.diff_attention_extend_paged(q, k_pool, v_pool, coef, tbl, pos, counts)
+        else:
+            # no extend plan for this head size: one paged decode per row, a padding row at length 0
+            zero = torch.zeros_like(pos)
+            out = torch.stack([ops.diff_attention_decode_paged(q[:, i], k_pool, v_pool, coef, tbl,
+                                                               torch.where(counts > i, pos + (i + 1), zero))
+                               for i in range(Tn)], dim=1)
+    if hasattr(attn, "group_norm"):
+        gn = attn.group_norm
+        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
+    return attn.dropout(attn.proj(out))
+
+
+def _paged_model_step(model, idx, cache: PagedKVCache, tbl, pos, counts, gather=None, one_row: bool = False):
+    """``_ragged_model_step`` over the page pool (``pos=None``: the prefill)."""
+    B, T = idx.shape
+    r = torch.arange(T, device=idx.device)
+    rows = r if pos is None else (pos[:, None].long() + r[None, :]).clamp_(max=model.block_size - 1)
+    x = model.token_embedding_table(idx)
+    if hasattr(model, "position_embedding_table"):
+        x = x + model.position_embedding_table(rows)
+    for layer, block in enumerate(model.blocks, 1):
+        x = x + _paged_attention_step(block, block.ln1(x), layer, cache, tbl, pos, counts, rows, one_row)
+        x = x + block.ffwd(block.ln2(x))
+    if gather is None:
+        return model.lm_head(model.ln_f(x))
+    x = x[torch.arange(B, device=idx.device), gather].unsqueeze(1)
+    return model.lm_head(model.ln_f(x))[:, 0]
+
+
+def _paged_gather(cache: PagedKVCache, seqs: Sequence[int]):
+    """The step's view of the device state: (slots, contiguous (B, max_pages) table, (B,) lengths)."""
+    cache._flush()
+    sl = torch.tensor([cache.slot[q] for q in seqs], device=cache.block_table.device)
+    return sl, cache.block_table.index_select(0, sl), cache.lengths.index_select(0, sl)
+
+
+@torch.no_grad()
+def prefill_paged(model, prompts: Sequence[torch.Tensor], cache: PagedKVCache):
+    """Add B prompts of different lengths (one-dimensional LongTensors, 1 .. block_size
+    tokens each) to ``cache`` -- an empty one or a live one, so new sequences join a
+    running batch -- in one fused right-padded causal forward, as ``prefill_ragged``:
+    pages are taken for every prompt (``OutOfPages``, before anything changes, if the
+    pool does not hold them), and each layer scatters its K_i / V rows
+    into them.  Returns (sequence ids, (B, vocab) logits at each prompt's last token)."""
+    bs = model.block_size
+    lens = []
+    for p in prompts:
+        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.long:
+            raise ValueError("prompts must be one-dimensional LongTensors")
+        if not 1 <= p.shape[0] <= bs:
+            raise ValueError(f"a prompt of {p.shape[0]} tokens is outside 1 .. block_size {bs}")
+        lens.append(p.shape[0])
+    if not lens:
+        raise ValueError("no prompts")
+    if not isinstance(cache, PagedKVCache):
+        raise ValueError("prefill_paged needs a PagedKVCache")
+    need = sum(cache._need(n) for n in lens)
+    if need > len(cache.free):
+        raise OutOfPages(f"{need} pages needed for {len(lens)} prompts, {len(cache.free)} of {cache.num_pages} free")
+    if len(lens) > len(cache.free_slots):
+        raise RuntimeError(f"{len(lens)} prompts, {len(cache.free_slots)} of {cache.max_seqs} sequence slots free "
+                           "(max_seqs)")
+    idx = torch.nn.utils.rnn.pad_sequence(list(prompts), batch_first=True)
+    cache._ensure(bs, idx.device)
+    seqs = []
+    for n in lens:
+        pages = [cache.free.pop() for _ in range(cache._need(n))]
+        for pg in pages:
+            cache.refcount[pg] = 1
+        seqs.append(cache._new_seq(pages, n))
+    _, tbl, counts = _paged_gather(cache, seqs)
+    last = torch.tensor(lens, device=idx.device) - 1
+    logits = _paged_model_step(model, idx, cache, tbl, None, counts, gather=last)
+    return seqs, logits
+
+
+@torch.no_grad()
+def decode_paged(model, seqs: Sequence[int], tok: torch.Tensor, cache: PagedKVCache,
+                 active: Optional[torch.Tensor] = None):
+    """``decode_ragged`` over any subset ``seqs`` (B ids) of the live sequences: ``tok``
+    (B, 1) is sequence seqs[b]'s token at its own length.  A sequence that crosses a page
+    boundary takes one page first, one about to write into a shared page copies it
+    (``OutOfPages`` before anything is written).  Returns (B, vocab) and advances the
+    lengths by one.
+
+    ``active``: optional device bool (B,), as for ``decode_ragged``: applied on the
+    device, so ``host_lengths`` becomes an upper bound, pages are taken for the bound and
+    ``sync()`` / ``release`` return the surplus."""
+    if tok.dim() != 2 or tok.shape[1] != 1:
+        raise ValueError("tok must be (B, 1)")
+    bs = model.block_size
+    if not isinstance(cache, PagedKVCache):
+        raise ValueError("decode_paged needs a PagedKVCache")
+    seqs = cache._check_live(seqs)
+    if len(seqs) != tok.shape[0]:
+        raise ValueError(f"batch size {tok.shape[0]} differs from the {len(seqs)} sequences named")
+    have = [cache.host_lengths[q] for q in seqs]
+    if active is None and max(have) + 1 > bs:
+        raise ValueError(f"a sequence is at block_size {bs}: positions are absolute within the window, "
+                         "the sliding window is the one-length path's job (last_logits)")
+    cache._prepare_writes(seqs, [min(n + 1, bs) for n in have])
+    sl, tbl, pos = _paged_gather(cache, seqs)
+    counts = torch.ones_like(pos) if active is None else active.to(torch.int32)
+    logits = _paged_model_step(model, tok, cache, tbl, pos, counts, one_row=True)[:, 0]
+    cache.lengths.index_copy_(0, sl, pos + counts)
+    for q, n in zip(seqs, have):
+        cache.host_lengths[q] = min(n + 1, bs)
+        if active is None and cache.host_low[q] == n:
+            cache.host_low[q] = n + 1
+    if active is not None:
+        cache.host_exact = False
+    return logits
+
+
+@torch.no_grad()
+def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cache: PagedKVCache,
+                 all_rows: bool = False):
+    """``append_ragged`` over any subset ``seqs`` of the live sequences: seqs[b] is fed the
+    first ``counts[b]`` tokens of ``new_idx[b]`` ((B, Tn), padded) at its own length, one
+    ``diff_attention_extend_paged`` per layer (head sizes without an extend plan: one
+    paged decode per row).  Pages are taken, and shared pages copied, for all of a
+    sequence's new rows first (``OutOfPages`` before anything is written).  Returns, raises
+    and splits the step near ``block_size`` as ``append_ragged`` does."""
+    if new_idx.dim() != 2 or new_idx.shape[1] < 1:
+        raise ValueError("new_idx must be (B, Tn) with Tn >= 1")
+    B, Tn = new_idx.shape
+    bs = model.block_size
+    if not isinstance(cache, PagedKVCache):
+        raise ValueError("append_paged needs a PagedKVCache")
+    seqs = cache._check_live(seqs)
+    if len(seqs) != B:
+        raise ValueError(f"batch size {B} differs from the {len(seqs)} sequences named")
+    cache.sync()
+    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+    if len(cnt) != B:
+        raise ValueError(f"{len(cnt)} counts for a batch of {B}")
+    have = [cache.host_lengths[q] for q in seqs]
+    for b, (c, n) in enumerate(zip(cnt, have)):
+        if not 0 <= c <= Tn:
+            raise ValueError(f"sequence {seqs[b]}: count {c} outside 0 .. {Tn}")
+        if n + c > bs:
+            raise ValueError(f"sequence {seqs[b]}: appending {c} tokens at length {n} crosses block_size {bs}")
+    writers = [b for b in range(B) if cnt[b] > 0]
+    cache._prepare_writes([seqs[b] for b in writers], [have[b] + cnt[b] for b in writers])
+    sl, tbl, lens = _paged_gather(cache, seqs)
+    dev = new_idx.device
+    cnt_dev = torch.tensor(cnt, dtype=torch.int32, device=dev)
+    out = None
+    done = 0
+    while done < Tn:
+        # the kernel needs pos[b] + width <= block_size of every sequence that still has real rows
+        live = [n + done for c, n in zip(cnt, have) if c > done]
+        w = min(Tn - done, bs - max(live)) if live else min(Tn - done, bs)
+        pos = lens + cnt_dev.clamp(max=done)
+        part_cnt = (cnt_dev - done).clamp_(0, w)
+        part_idx = new_idx[:, done:done + w]
+        if all_rows:
+            part = _paged_model_step(model, part_idx, cache, tbl, pos, part_cnt)
+            out = part if out is None else torch.cat([out, part], dim=1)
+        else:
+            last = (cnt_dev.long() - 1 - done).clamp_(0, w - 1)
+            part = _paged_model_step(model, part_idx, cache, tbl, pos, part_cnt, gather=last)
+            here = ((cnt_dev > done) | (done == 0))[:, None]
+            out = part if out is None else torch.where(here, part, out)
+        done += w
+    cache.lengths.index_copy_(0, sl, lens + cnt_dev)
+    for q, n, c in zip(seqs, have, cnt):
+        cache.host_lengths[q] = cache.host_low[q] = n + c
+    return out
+
+
+@torch.no_grad()
+def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
+                   n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64):
+    """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
+    (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
+    window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
+    same ``eos_id`` handling.  Returns a list of B one-dimensional tensors.
+
+    ``n_samples > 1``: every prompt is prefilled once and forked ``n_samples - 1`` times,
+    so its samples share the prompt's full pages (a partial last page is copied when a
+    sample first writes into it); the batch is sample-major within a prompt, and the
+    result is a list of B lists of ``n_samples`` tensors.  ``num_pages``: the pool size;
+    default the exact need of the call (``OutOfPages`` if a given one is too small)."""
+    bs = model.block_size
+    if n_samples < 1:
+        raise ValueError("n_samples must be >= 1")
+    for p in prompts:
+        if p.shape[0] + max_new_tokens > bs:
+            raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
+                             f"block_size {bs}: the sliding window is the one-length path's job")
+    if num_pages is None:
+        num_pages = 0
+        for p in prompts:
+            n, end = p.shape[0], p.shape[0] + max(max_new_tokens - 1, 0)       # the last sample is never cached
+            shared = n // page_size if end > n else -(-n // page_size)         # nothing written: all pages shared
+            num_pages += shared + n_samples * (-(-end // page_size) - shared)
+        num_pages = max(num_pages, 1)
+    cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1))
+    roots, logits = prefill_paged(model, prompts, cache)
+    seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
+    outs = [p for p in prompts for _ in range(n_samples)]
+    if max_new_tokens >= 1:
+        if n_samples > 1:
+            logits = logits.repeat_interleave(n_samples, dim=0)
+        active = None if eos_id is None else torch.ones(len(seqs), dtype=torch.bool, device=logits.device)
+        new = []
+        for step in range(max_new_tokens):
+            probs = F.softmax(logits, dim=-1)
+            tok = torch.multinomial(probs, num_samples=1)
+            new.append(tok)
+            if step + 1 == max_new_tokens:
+                break
+            if active is not None:
+                active = active & (tok[:, 0] != eos_id)
+            logits = decode_paged(model, seqs, tok, cache, active)
+        toks = torch.cat(new, dim=1)
+        keep = [max_new_tokens] * len(seqs)
+        if eos_id is not None:
+            hit = toks == eos_id
+            first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
+            keep = first.tolist()
+        outs = [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(outs)]
+    else:
+        outs = [p.clone() for p in outs]
+    if n_samples == 1:
+        return outs
+    return [outs[b * n_samples:(b + 1) * n_samples] for b in range(len(prompts))]

@@ -855,3 +855,101 @@ def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
                               coef.data_ptr(), pos.data_ptr(), None if counts is None else counts.data_ptr())
     _lib.check(lib.dta_attn_extend_ragged(a, _lib.stream_handle(q.device)))
     return o.view(B, Tq, H * dv)
+
+
+# ------------------------------------------------------------------- paged ---
+PAGE_SIZES = (32, 64, 128, 256)
+
+
+def _paged_views(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, B: int, H: int, N: int, hs: int):
+    """Checks shared by the two paged ops; returns (n_pages, P, max_pages, dv)."""
+    if k_pool.dim() != 5 or v_pool.dim() != 4:
+        raise RuntimeError("k_pool must be (n_pages, P, H, N, hs) and v_pool (n_pages, P, H, dv)")
+    n_pages, P, dv = k_pool.shape[0], k_pool.shape[1], v_pool.shape[-1]
+    if P not in PAGE_SIZES:
+        raise RuntimeError(f"page size {P} is not one of {PAGE_SIZES}")
+    if n_pages < 1:
+        raise RuntimeError("the pool holds no page")
+    if tuple(k_pool.shape) != (n_pages, P, H, N, hs) or tuple(v_pool.shape) != (n_pages, P, H, dv):
+        raise RuntimeError("k_pool/v_pool shapes do not match q")
+    if q.dtype != k_pool.dtype or q.dtype != v_pool.dtype:
+        raise RuntimeError("q, k_pool and v_pool must share a dtype")
+    if (not isinstance(block_table, Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != q.device):
+        raise RuntimeError(f"block_table must be a device int32 tensor of shape ({B}, max_pages) on {q.device}")
+    if not block_table.is_contiguous():
+        raise RuntimeError("block_table must be contiguous")
+    return n_pages, P, block_table.shape[1], dv
+
+
+def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
+                                lengths: Tensor, max_length: Optional[int] = None) -> Tensor:
+    """``diff_attention_decode_ragged`` over a paged cache: key row j of sequence b is
+    row ``j % P`` of pool page ``block_table[b, j // P]``.
+
+    q: (B, H, N, hs); k_pool: (n_pages, P, H, N, hs); v_pool: (n_pages, P, H, dv) (strided
+    views of one packed pool, innermost dim contiguous), P in 32, 64, 128, 256;
+    ``block_table``: contiguous device int32 (B, max_pages); ``lengths``: device int32 (B,).
+    The logical capacity is T_cap = max_pages * P, and ``max_length`` (default T_cap) the
+    host upper bound of every length.  Only table entries below ceil(lengths[b] / P) are
+    read (the rest may hold anything, e.g. -1) and every id read is clamped into the pool;
+    rows past a length and pages nobody names may hold NaN.  Cut a contiguous cache
+    (B, T_cap, ...) into pages placed anywhere in the pool: the result is bitwise that of
+    ``diff_attention_decode_ragged`` on the contiguous cache.  Returns (B, H*dv)."""
+    lib = _lib.load()
+    _require_gpu(q, k_pool, v_pool, coef)
+    B, H, N, hs = q.shape
+    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
+    T_cap = max_pages * P
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    _batch_int32(lengths, B, q, "lengths")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
+    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    a = _lib.DecodePagedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
+                             _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_pool), _lib.tensor5(v_pool),
+                             _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr(),
+                             P, max_pages, n_pages, block_table.data_ptr())
+    _lib.check(lib.dta_attn_decode_paged(a, _lib.stream_handle(q.device)))
+    return o.view(B, H * dv)
+
+
+def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
+                                pos: Tensor, counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_extend_ragged`` over a paged cache (pool views and ``block_table``
+    as for ``diff_attention_decode_paged``): sequence b appends ``counts[b]`` real rows at
+    ``pos[b]``, its cache rows 0 .. pos[b]+counts[b]-1 reached through its table row
+    (entries below ceil((pos[b] + counts[b]) / P) are read).  q: (B, Tq, H, N, hs) padded;
+    rows r >= counts[b] come back as zeros.  The kernel clamps pos[b] to
+    [0, max_pages * P - Tq].  Bitwise equal to ``diff_attention_extend_ragged`` on the
+    gathered contiguous cache.  Returns (B, Tq, H*dv).  No fallback: raises for a shape
+    without a kernel plan (``extend_supported``)."""
+    lib = _lib.load()
+    _require_gpu(q, k_pool, v_pool, coef)
+    if q.dim() != 5:
+        raise RuntimeError("q must be (B, Tq, H, N, hs)")
+    B, Tq, H, N, hs = q.shape
+    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
+    T_cap = max_pages * P
+    if tuple(coef.shape) != (H, N):
+        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+    _batch_int32(pos, B, q, "pos")
+    if counts is not None:
+        _batch_int32(counts, B, q, "counts")
+    if Tq > T_cap:
+        raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
+    if not extend_supported(q.dtype, hs, N, dv):
+        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
+    if B * Tq == 0:
+        return o.view(B, Tq, H * dv)
+    a = _lib.ExtendPagedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, T_cap, 1.0 / math.sqrt(hs),
+                             _lib.tensor5(q), _lib.tensor5(k_pool), _lib.tensor5(v_pool), _lib.tensor5(o),
+                             coef.data_ptr(), pos.data_ptr(), None if counts is None else counts.data_ptr(),
+                             P, max_pages, n_pages, block_table.data_ptr())
+    _lib.check(lib.dta_attn_extend_paged(a, _lib.stream_handle(q.device)))
+    return o.view(B, Tq, H * dv)

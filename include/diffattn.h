@@ -47,6 +47,8 @@ extern "C" {
                                   still 9, added without a bump (no existing struct or entry point changed):
                                   dta_attn_decode_ragged, dta_attn_extend_ragged (per-sequence lengths) -- the
                                   presence of the symbols is the capability check (dlsym / hasattr);
+                                  still 9, added the same way: dta_attn_decode_paged, dta_attn_extend_paged
+                                  (block-table KV cache over a pool of pages);
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -371,6 +373,71 @@ typedef struct dta_attn_extend_ragged_args {
   const int32_t* count_dev;  /* device int32 [B] or NULL: real new rows of sequence b */
 } dta_attn_extend_ragged_args;
 int dta_attn_extend_ragged(const dta_attn_extend_ragged_args* a, void* stream);
+
+/* Paged KV cache: dta_attn_decode_ragged / dta_attn_extend_ragged with the cache rows
+ * reached through a per-sequence block table into a shared pool of fixed-size pages, so
+ * a batch holds sum_b ceil(len_b / P) pages instead of B * t_cap rows, a finished
+ * sequence's pages go to a new one, and sequences with a common prefix share its pages.
+ * Replaces the same reference lines (the per-token full-prefix recompute of generate(),
+ * diff_transformer.py:177-185; Ndiff_transformer.py generate; control.py:163-171, and
+ * diff_transformer.py:57-72 for the newest rows).
+ *   k_pool [page][row < P][h][i][d]   sb = page stride, st = row stride
+ *   v_pool [page][row < P][h][e]
+ *   block_table_dev  device int32 [B][max_pages], contiguous
+ * Key row j of sequence b is pool[block_table_dev[b][j / P]][j % P]:
+ *   decode:  o[b] = sum_i coef[h][i] * softmax(q_i[b] . K_i(b, 0:len_b)^T * scale) V(b, 0:len_b)
+ *   extend:  dta_attn_extend_ragged's formula with K_i[b][j] = K_i(b, j), V[b][j] = V(b, j)
+ * page_size P is 32, 64, 128 or 256 (the multiples of the extend kernel's 32-key tile
+ * that divide the decode chunk: a decode chunk is a whole number of pages and a key tile
+ * never straddles a page); t_cap, the logical capacity of a sequence, must equal
+ * max_pages * page_size and plays t_cap's part in the ragged calls (workspace size
+ * dta_attn_decode_workspace_bytes(.., t_cap), chunk choice, the clamp of pos_b to
+ * [0, t_cap - Tq]); n_pages is the number of pages the pool views hold.
+ * Table entries: only entries p < ceil(len_b / P) of row b are read (extend:
+ * p < ceil((pos_b + count_b) / P)); the rest may hold anything.  Every id that is read is
+ * clamped to [0, n_pages - 1] before it forms an address, as len_b, pos_b and count_b are
+ * clamped, so no device value can index outside the pool.  Rows >= len_b inside a used
+ * page, and every page no used entry names, may hold anything, NaN included.  A decode
+ * chunk wholly past len_b exits before it touches memory; len_b == 0 writes zeros; extend
+ * writes zeros to rows count_b .. Tq-1 and a query tile without a real row exits.
+ * Bitwise relation: the kernels do the ragged kernels' operations in the same order, only
+ * the addresses differ.  Cut a contiguous cache (B, max_pages * P, ..) into pages, place
+ * them anywhere in a pool and describe them by a block table: the outputs equal
+ * dta_attn_decode_ragged / dta_attn_extend_ragged on the contiguous cache bit for bit, at
+ * the same t_cap.
+ * Errors: everything the ragged entry points reject, and DTA_ERR_INVALID for a null or
+ * not 4-byte aligned block_table_dev, a page_size outside {32, 64, 128, 256},
+ * n_pages < 1, max_pages < 1 or t_cap != max_pages * page_size.  dta_extend_supported is
+ * the capability check of the extend call. */
+typedef struct dta_attn_decode_paged_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t length;            /* host upper bound of every lengths_dev[b] (<= t_cap); sizes the grid */
+  int32_t t_cap;             /* = max_pages * page_size; workspace row length */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* lengths_dev;/* device int32 [B], required: valid cached keys of sequence b */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+} dta_attn_decode_paged_args;
+int dta_attn_decode_paged(const dta_attn_decode_paged_args* a, void* stream);
+
+typedef struct dta_attn_extend_paged_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded) */
+  int32_t t_cap;             /* = max_pages * page_size (>= Tq) */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;
+  const float* coef;         /* fp32 [h][i] */
+  const int32_t* pos_dev;    /* device int32 [B]: absolute position of query row 0 of sequence b */
+  const int32_t* count_dev;  /* device int32 [B] or NULL: real new rows of sequence b */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+} dta_attn_extend_paged_args;
+int dta_attn_extend_paged(const dta_attn_extend_paged_args* a, void* stream);
 
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
