@@ -31,7 +31,12 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # ragged batches, added within ABI 9: their presence is the capability check
            "dta_attn_decode_ragged", "dta_attn_extend_ragged",
            # paged caches (block table over a pool of pages), added the same way
-           "dta_attn_decode_paged", "dta_attn_extend_paged")
+           "dta_attn_decode_paged", "dta_attn_extend_paged",
+           # fp8 (e4m3fn) pages with per-(row, head) scales, added the same way
+           "dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
+# the entry points an older library of the same ABI may lack without being unusable
+# (``ops.fp8_cache_supported``)
+FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
 
 
 class DtaTensor(ctypes.Structure):
@@ -152,6 +157,19 @@ class ExtendPagedArgs(ctypes.Structure):
                 ("block_table_dev", ctypes.c_void_p)]
 
 
+class DecodePagedFp8Args(ctypes.Structure):
+    _fields_ = DecodePagedArgs._fields_ + [("scale_pool_dev", ctypes.c_void_p), ("scale_page_stride", ctypes.c_int64)]
+
+
+class KvQuantRowsArgs(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Tn", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
+                ("page_size", ctypes.c_int32), ("n_pages", ctypes.c_int32),
+                ("k_new", DtaTensor), ("v_new", DtaTensor), ("k_pool", DtaTensor), ("v_pool", DtaTensor),
+                ("scale_pool_dev", ctypes.c_void_p), ("scale_page_stride", ctypes.c_int64),
+                ("slot_dev", ctypes.c_void_p)]
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -203,10 +221,19 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                    "dta_attn_bwd_dkdv_groups", "dta_attn_extend", "dta_extend_supported", "dta_attn_decode_ragged",
                    "dta_attn_extend_ragged", "dta_attn_decode_paged", "dta_attn_extend_paged"):
             getattr(lib, fn).restype = ctypes.c_int
+        if fp8_symbols(lib):
+            lib.dta_attn_decode_paged_fp8.argtypes = [P(DecodePagedFp8Args), ctypes.c_void_p]
+            lib.dta_kv_quant_rows.argtypes = [P(KvQuantRowsArgs), ctypes.c_void_p]
+            lib.dta_attn_decode_paged_fp8.restype = lib.dta_kv_quant_rows.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
         return lib
+
+
+def fp8_symbols(lib) -> bool:
+    """Whether ``lib`` exports the fp8-cache entry points (they arrived inside ABI 9)."""
+    return all(hasattr(lib, name) for name in FP8_EXPORTS)
 
 
 def check(rc: int) -> None:

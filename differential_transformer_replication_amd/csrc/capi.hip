@@ -504,18 +504,28 @@ static bool page_table(const A* a, PageTable& g) {
   return true;
 }
 
-// kc / vc: the cache views (contiguous [b][t], or with a table in pg the page pool)
+// a pool of e4m3fn bytes (strides in bytes): 16-byte pointer, page and row strides; heads and
+// branches start on the widest load a lane makes of them (16 bytes, 8 where head_size % 16)
+static bool ok_byte_pool(const dta_tensor& t, int width, bool with_i) {
+  const int64_t v = width % 16 ? 8 : 16;
+  if (!aligned_ptr(t.ptr) || t.sb % 16 || t.st % 16 || t.sh % v || (with_i && t.si % v)) return false;
+  return t.sb >= 0 && t.st >= 0 && t.sh >= 0 && t.si >= 0;
+}
+
+// kc / vc: the cache views (contiguous [b][t], or with a table in pg the page pool);
+// scales: NULL, or the fp32 scale pool of an fp8 page pool (kc / vc are then byte views)
 extern "C++" template <class A>
 static int decode_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const int32_t* ldev, int lsb,
-                       const PageTable& pg, void* stream) {
+                       const PageTable& pg, void* stream, const float* scales = nullptr, int64_t scales_sb = 0) {
   if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (a->head_size % 8 || a->head_size > 128 || a->n_terms > 4 || a->dv > 256) return DTA_ERR_UNSUPPORTED;
   if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
   if ((int64_t)a->B * a->H == 0) return DTA_OK;
   // every operand is read or written by 16-byte vector accesses: full alignment checks on all four
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(kc, a->dtype, true) ||
-      !ok_tensor(vc, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef ||
-      !aligned_ptr(a->workspace))
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
+    return DTA_ERR_INVALID;
+  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
+             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
     return DTA_ERR_INVALID;
   DecodeParams p{};
   p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
@@ -524,6 +534,10 @@ static int decode_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, c
   p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = ldev; p.Lsb = lsb;
   p.S = (int)decode_splits(a->length);
   p.ml = a->workspace + (int64_t)a->B * a->H * p.S * a->n_terms * a->dv;   // after the partial rows
+  if (scales) {
+    p.kvs = scales; p.kvs_sb = scales_sb;
+    return status(launch_decode_f8(a->dtype, p, (hipStream_t)stream));
+  }
   return status(launch_decode(a->dtype, p, (hipStream_t)stream));
 }
 
@@ -541,6 +555,44 @@ int dta_attn_decode_paged(const dta_attn_decode_paged_args* a, void* stream) {
   PageTable pg{};
   if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
   return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream);
+}
+
+int dta_attn_decode_paged_fp8(const dta_attn_decode_paged_fp8_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
+  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
+  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
+    return DTA_ERR_INVALID;
+  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, a->scale_pool_dev, a->scale_page_stride);
+}
+
+int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream) {
+  if (!a || !ok_dims(a->dtype, a->B, a->Tn, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (a->head_size % 16 || a->dv % 16 || a->head_size > 128 || a->dv > 256 || a->n_terms > 4)
+    return DTA_ERR_UNSUPPORTED;
+  int shift = 0;
+  switch (a->page_size) {
+    case 32: shift = 5; break;
+    case 64: shift = 6; break;
+    case 128: shift = 7; break;
+    case 256: shift = 8; break;
+    default: return DTA_ERR_INVALID;
+  }
+  if (a->n_pages < 1 || ((int64_t)a->n_pages + 1) * a->page_size > INT32_MAX) return DTA_ERR_INVALID;
+  if (!a->slot_dev || (uintptr_t)a->slot_dev % 4 || !a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4 ||
+      a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
+    return DTA_ERR_INVALID;
+  if ((int64_t)a->B * a->Tn == 0) return DTA_OK;
+  if (!ok_tensor(a->k_new, a->dtype, true) || !ok_tensor(a->v_new, a->dtype, false) ||
+      !ok_byte_pool(a->k_pool, a->head_size, true) || !ok_byte_pool(a->v_pool, a->dv, false))
+    return DTA_ERR_INVALID;
+  KvQuantParams p{};
+  p.ksrc = t5(a->k_new); p.vsrc = t5(a->v_new); p.kdst = t5(a->k_pool); p.vdst = t5(a->v_pool);
+  p.kvs = a->scale_pool_dev; p.kvs_sb = a->scale_page_stride; p.slot = a->slot_dev;
+  p.B = a->B; p.Tn = a->Tn; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
+  p.shift = shift; p.slots = (a->n_pages + 1) * a->page_size;
+  return status(launch_kv_quant(a->dtype, p, (hipStream_t)stream));
 }
 
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {

@@ -49,6 +49,54 @@ __device__ __forceinline__ void ld8f(const E* p, float* f) {
   }
 }
 
+// ---- fp8 cache rows (dta_attn_decode_paged_fp8) -------------------------------------
+// The cache element type C is a template parameter next to E (the type of q and o).  With
+// C = E every expression below is the one it was; C = f8e4 reads OCP e4m3fn bytes
+// (v_cvt_pk_f32_fp8) and one fp32 scale per (row, head, K_i | V) from kvs:
+//   score_ij = (q_i . byte(K_i[j])) * k_scale[j][h][i]     one multiply per (row, branch)
+//   acc_i   += (e_ij * v_scale[j][h]) * byte(V[j])          the row sum l_i keeps e_ij
+// The split kernel asks for the scales of a chunk once, thread = key, before phase 1, and applies
+// both in phase 2, where a thread owns a key anyway.  A lane reads DTA_F8_KB bytes of a K row
+// and DTA_F8_VB bytes of a V row (8 or 16: the A/B is in DESIGN.md).  Rows >= len_b, their
+// scales included, are never loaded.
+struct f8e4 { uint8_t b; };
+template <class C> inline constexpr bool is_f8 = false;
+template <> inline constexpr bool is_f8<f8e4> = true;
+#ifndef DTA_F8_KB
+#define DTA_F8_KB 16
+#endif
+#ifndef DTA_F8_VB
+#define DTA_F8_VB 8        // 16 doubles the V row groups and `part`, and halves the occupancy: slower (A/B)
+#endif
+static_assert((DTA_F8_KB == 8 || DTA_F8_KB == 16) && (DTA_F8_VB == 8 || DTA_F8_VB == 16), "8 or 16 bytes per lane");
+
+// n (8 or 16) cache elements at p as floats
+template <class C, int n, bool NT = false>
+__device__ __forceinline__ void ldnf(const C* p, float* f) {
+  if constexpr (is_f8<C>) {
+    typedef uint32_t uv __attribute__((ext_vector_type(n / 4)));
+    const uv v = NT ? __builtin_nontemporal_load(reinterpret_cast<const uv*>(p)) : *reinterpret_cast<const uv*>(p);
+#pragma unroll
+    for (int w = 0; w < n / 4; ++w) {
+      const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], false);
+      const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], true);
+      f[4 * w] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
+    }
+  } else {
+    static_assert(n == 8, "16- and 32-bit caches are read 8 elements per lane");
+    ld8f<C, NT>(p, f);
+  }
+}
+template <class C>
+__device__ __forceinline__ float ld1f(const C* p) {
+  if constexpr (is_f8<C>) return __builtin_amdgcn_cvt_f32_fp8((int)p->b, 0);
+  else return (float)*p;
+}
+// the N + 1 scales of cache row j of sequence b, head h (paged only)
+__device__ __forceinline__ const float* scale_row(const DecodeParams& p, int page, int r, int h, int N) {
+  return p.kvs + (int64_t)page * p.kvs_sb + ((int64_t)r * p.H + h) * (N + 1);
+}
+
 __device__ __forceinline__ float wmax(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -95,8 +143,10 @@ __device__ __forceinline__ int64_t row_off(const DecodeParams& p, const T5& t, i
   else return b * t.sb + (int64_t)j * t.st;
 }
 
-template <class E, int N, bool PG>
+template <class E, int N, bool PG, class C>
 __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
+  constexpr bool F8 = is_f8<C>;
+  static_assert(!F8 || PG, "the fp8 cache is a paged cache");
   __shared__ float qs[N * 128];
   __shared__ float red[kWaves * N];
   __shared__ float part[kThreads];
@@ -107,22 +157,24 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   __syncthreads();
 
   float* ws = p.ws + ((int64_t)b * p.H + h) * N * p.ldw;     // [i][ldw]
-  const E* gk = reinterpret_cast<const E*>(p.k.p) + h * p.k.sh;
+  const C* gk = reinterpret_cast<const C*>(p.k.p) + h * p.k.sh;
+  [[maybe_unused]] const int pmask = (1 << p.pg.shift) - 1;
   float m[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) m[i] = -INFINITY;
   for (int j = tid; j < L; j += kThreads) {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      const E* kr = gk + row_off<PG>(p, p.k, b, j) + i * p.k.si;
+      const C* kr = gk + row_off<PG>(p, p.k, b, j) + i * p.k.si;
       float s = 0.f;
       for (int d = 0; d < HS; d += 8) {
         float f[8];
-        ld8f<E>(kr + d, f);
+        ldnf<C, 8>(kr + d, f);
 #pragma unroll
         for (int u = 0; u < 8; ++u) s = fmaf(qs[i * HS + d + u], f[u], s);
       }
-      s *= p.scale;
+      if constexpr (F8) s *= p.scale * scale_row(p, page_of(p.pg, b, j), j & pmask, h, N)[i];
+      else s *= p.scale;
       ws[i * p.ldw + j] = s;
       m[i] = fmaxf(m[i], s);
     }
@@ -148,6 +200,7 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
     float w = 0.f;
 #pragma unroll
     for (int i = 0; i < N; ++i) w = fmaf(c[i], ws[i * p.ldw + j], w);
+    if constexpr (F8) w *= scale_row(p, page_of(p.pg, b, j), j & pmask, h, N)[N];   // V's scale, after the l_i
     ws[j] = w;                                  // row 0 now holds the combined map row
   }
   __threadfence_block();
@@ -156,10 +209,10 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
   // phase 4: G key groups x DV columns
   const int G = kThreads / DV;
   const int g = tid / DV, e = tid % DV;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + h * p.v.sh + e;
+  const C* gv = reinterpret_cast<const C*>(p.v.p) + h * p.v.sh + e;
   float acc = 0.f;
   if (g < G)
-    for (int j = g; j < L; j += G) acc = fmaf(ws[j], (float)gv[row_off<PG>(p, p.v, b, j)], acc);
+    for (int j = g; j < L; j += G) acc = fmaf(ws[j], ld1f<C>(gv + row_off<PG>(p, p.v, b, j)), acc);
   part[tid] = acc;
   __syncthreads();
   if (tid < DV) {
@@ -176,17 +229,27 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
 // un-normalised row acc_i = sum_j exp(s_ij - m_i) V_j (fp32).  decode_combine
 // rescales the S partials to the global max and applies coef_i / L_i.
 // K rows are read by LPR = HS/8 lanes each (one 16-byte load per lane), V rows
-// by DV/8 lanes each, so every wave-level load is a run of whole rows.
+// by DV/8 lanes each, so every wave-level load is a run of whole rows.  (fp8 cache:
+// HS / kF8KB and DV / kF8VB lanes, one 8- or 16-byte load per lane.)
 // kChunk: keys per split workgroup.  DTA_DECODE_CHUNK (256) sizes the workspace
 // (the most splits); launches with >= kWideGrid workgroups use 2x chunks, which
 // halves the partials (A/B: +4.5% at B=8 H=16 L=32768, slower on smaller grids)
 constexpr int kWideGrid = 8192;
 
-template <class E, int N, int HS, int DV, int kChunk, bool PG>
+// fp8: 16 bytes per lane of a V row doubles the row groups G and with them `part`; shapes where
+// that would pass 40 KiB of LDS read V 8 bytes per lane
+template <class C, int N, int DV>
+inline constexpr int v_lane_elems = !is_f8<C> ? 8 : (kThreads / (DV / DTA_F8_VB)) * N * (DV + 4) * 4 <= 40960 ? DTA_F8_VB : 8;
+
+template <class E, int N, int HS, int DV, int kChunk, bool PG, class C>
 __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) {
-  constexpr int LPR = HS / 8;                 // lanes per K row
+  constexpr bool F8 = is_f8<C>;
+  static_assert(!F8 || PG, "the fp8 cache is a paged cache");
+  constexpr int KE = F8 ? DTA_F8_KB : 8;      // K elements per lane
+  constexpr int VE = v_lane_elems<C, N, DV>;  // V elements per lane
+  constexpr int LPR = HS / KE;                // lanes per K row
   constexpr int KPW = 64 / LPR;               // keys per wave per load
-  constexpr int VPR = DV / 8;                 // lanes per V row
+  constexpr int VPR = DV / VE;                // lanes per V row
   constexpr int G = kThreads / VPR;           // V row groups
   constexpr int KPT = kChunk / kThreads;      // keys per thread in the softmax phase
   static_assert(kChunk % kThreads == 0, "chunk must be a multiple of the workgroup");
@@ -213,28 +276,42 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     else return b * t.sb + (int64_t)(j0 + jj) * t.st;
   };
 
+  // fp8: the scales of this thread's phase-2 keys (K_i: [0, N), V: [N]), asked for here so that
+  // they arrive under the K stream; after the early exit and the page list, as every load is
+  [[maybe_unused]] float ksc[F8 ? KPT : 1][N + 1];
+  if constexpr (F8) {
+#pragma unroll
+    for (int r = 0; r < KPT; ++r) {
+      const int j = tid + r * kThreads;
+      const float* sp = scale_row(p, pgs[min(j, nk - 1) >> psh], j & pmask, h, N);
+#pragma unroll
+      for (int x = 0; x <= N; ++x) ksc[r][x] = j < nk ? sp[x] : 0.f;
+    }
+  }
+
   // phase 1: scores of this chunk into LDS
   {
     const int sub = lane % LPR, kr = lane / LPR;
-    const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh + sub * 8;
-    float q[N][8];
+    const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh + sub * KE;
+    float q[N][KE];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      ld8f<E>(gq + i * p.q.si, q[i]);
 #pragma unroll
-      for (int u = 0; u < 8; ++u) q[i][u] *= p.scale;
+      for (int c = 0; c < KE; c += 8) ld8f<E>(gq + i * p.q.si + c, q[i] + c);
+#pragma unroll
+      for (int u = 0; u < KE; ++u) q[i][u] *= p.scale;
     }
-    const E* gk = reinterpret_cast<const E*>(p.k.p) + h * p.k.sh + sub * 8;
+    const C* gk = reinterpret_cast<const C*>(p.k.p) + h * p.k.sh + sub * KE;
     for (int jj = wave * KPW + kr; jj < kChunk; jj += kWaves * KPW) {
       const bool ok = jj < nk;
-      const E* kp = gk + crow(p.k, ok ? jj : 0);
+      const C* kp = gk + crow(p.k, ok ? jj : 0);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        float f[8];
-        ld8f<E, DTA_DEC_NT>(kp + i * p.k.si, f);
+        float f[KE];
+        ldnf<C, KE, DTA_DEC_NT>(kp + i * p.k.si, f);
         float d = 0.f;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) d = fmaf(q[i][u], f[u], d);
+        for (int u = 0; u < KE; ++u) d = fmaf(q[i][u], f[u], d);
 #pragma unroll
         for (int o = LPR / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
         if (sub == 0) sc[i][jj] = ok ? d : -INFINITY;
@@ -247,9 +324,20 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   float m[N], l[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    m[i] = sc[i][tid];
+    if constexpr (F8) {
+      // the row's K_i scale: once per (row, branch); rows >= nk keep their -inf
+      m[i] = -INFINITY;
 #pragma unroll
-    for (int r = 1; r < KPT; ++r) m[i] = fmaxf(m[i], sc[i][tid + r * kThreads]);
+      for (int r = 0; r < KPT; ++r) {
+        const int j = tid + r * kThreads;
+        if (j < nk) sc[i][j] *= ksc[r][i];
+        m[i] = fmaxf(m[i], sc[i][j]);
+      }
+    } else {
+      m[i] = sc[i][tid];
+#pragma unroll
+      for (int r = 1; r < KPT; ++r) m[i] = fmaxf(m[i], sc[i][tid + r * kThreads]);
+    }
   }
   block_reduce<N, true>(m, red);
 #pragma unroll
@@ -259,34 +347,35 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     for (int r = 0; r < KPT; ++r) {
       const int j = tid + r * kThreads;
       const float e = j < nk ? __expf(sc[i][j] - m[i]) : 0.f;
-      sc[i][j] = e;
+      if constexpr (F8) sc[i][j] = e * ksc[r][N];      // V's scale rides on the probability; l_i does not see it
+      else sc[i][j] = e;
       l[i] += e;
     }
   }
   block_reduce<N, false>(l, red);        // its barriers also publish sc
 
-  // phase 3: acc_i = sum_j e_ij V_j (thread = 8 columns of one row group)
-  const int g = tid / VPR, c0 = (tid % VPR) * 8;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + h * p.v.sh + c0;
-  float acc[N][8];
+  // phase 3: acc_i = sum_j e_ij V_j (thread = VE columns of one row group)
+  const int g = tid / VPR, c0 = (tid % VPR) * VE;
+  const C* gv = reinterpret_cast<const C*>(p.v.p) + h * p.v.sh + c0;
+  float acc[N][VE];
 #pragma unroll
   for (int i = 0; i < N; ++i)
 #pragma unroll
-    for (int u = 0; u < 8; ++u) acc[i][u] = 0.f;
+    for (int u = 0; u < VE; ++u) acc[i][u] = 0.f;
   for (int jj = g; jj < nk; jj += G) {
-    float f[8];
-    ld8f<E, DTA_DEC_NT>(gv + crow(p.v, jj), f);
+    float f[VE];
+    ldnf<C, VE, DTA_DEC_NT>(gv + crow(p.v, jj), f);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const float e = sc[i][jj];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc[i][u] = fmaf(e, f[u], acc[i][u]);
+      for (int u = 0; u < VE; ++u) acc[i][u] = fmaf(e, f[u], acc[i][u]);
     }
   }
 #pragma unroll
   for (int i = 0; i < N; ++i)
 #pragma unroll
-    for (int u = 0; u < 8; ++u) part[g][i][c0 + u] = acc[i][u];
+    for (int u = 0; u < VE; ++u) part[g][i][c0 + u] = acc[i][u];
   __syncthreads();
   const int64_t row = ((int64_t)b * p.H + h) * p.S + s;      // partial index
   float* wacc = p.ws + row * N * DV;
@@ -349,54 +438,54 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
 // current length, so the eager path (length = pos + 1) and the graph path
 // (length = t_cap, device length) launch the same chunks and reduce in the same
 // order: their outputs are bitwise equal at every position.
-template <class E, int N, int HS, int DV, bool PG>
+template <class E, int N, int HS, int DV, bool PG, class C>
 int split_launch(const DecodeParams& p0, hipStream_t st) {
-  constexpr int C = DTA_DECODE_CHUNK;
-  const int64_t s_cap = (p0.ldw + C - 1) / C;
+  constexpr int kC = DTA_DECODE_CHUNK;
+  const int64_t s_cap = (p0.ldw + kC - 1) / kC;
   const bool wide = s_cap * p0.H * p0.B >= kWideGrid;
-  const int chunk = wide ? 2 * C : C;
+  const int chunk = wide ? 2 * kC : kC;
   // the combine keeps one LDS weight per (chunk, branch): gate on the chunk actually launched
   if (((int64_t)p0.ldw + chunk - 1) / chunk * N > kMaxPartials) return 1;
   DecodeParams p = p0;
   p.S = (p0.L + chunk - 1) / chunk;            // same partial layout as C-key chunks, fewer rows used
   if (wide) {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * C, PG>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
-    hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * C>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * kC, PG, C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * kC>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
   } else {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, C, PG>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
-    hipLaunchKernelGGL((decode_combine_kernel<E, N, C>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, kC, PG, C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, kC>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
   }
   return (int)hipGetLastError();
 }
 
-template <class E, int N, bool PG>
+template <class E, int N, bool PG, class C>
 int split_dispatch(const DecodeParams& p, hipStream_t st) {
-  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64, PG>(p, st);
-  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128, PG>(p, st);
-  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256, PG>(p, st);
-  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64, PG>(p, st);
-  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128, PG>(p, st);
+  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64, PG, C>(p, st);
+  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128, PG, C>(p, st);
+  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256, PG, C>(p, st);
+  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64, PG, C>(p, st);
+  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128, PG, C>(p, st);
   return 1;    // no split plan: caller uses the single-pass kernel
 }
 
-template <class E, bool PG>
+template <class E, bool PG, class C = E>
 int decode_launch(const DecodeParams& p, hipStream_t st) {
   if (p.ml) {
     int e = 1;
     switch (p.N) {
-      case 1: e = split_dispatch<E, 1, PG>(p, st); break;
-      case 2: e = split_dispatch<E, 2, PG>(p, st); break;
-      case 3: e = split_dispatch<E, 3, PG>(p, st); break;
-      case 4: e = split_dispatch<E, 4, PG>(p, st); break;
+      case 1: e = split_dispatch<E, 1, PG, C>(p, st); break;
+      case 2: e = split_dispatch<E, 2, PG, C>(p, st); break;
+      case 3: e = split_dispatch<E, 3, PG, C>(p, st); break;
+      case 4: e = split_dispatch<E, 4, PG, C>(p, st); break;
     }
     if (e != 1) return e;
   }
   dim3 g(p.H, p.B);
   switch (p.N) {
-    case 1: hipLaunchKernelGGL((decode_kernel<E, 1, PG>), g, dim3(kThreads), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((decode_kernel<E, 2, PG>), g, dim3(kThreads), 0, st, p); break;
-    case 3: hipLaunchKernelGGL((decode_kernel<E, 3, PG>), g, dim3(kThreads), 0, st, p); break;
-    case 4: hipLaunchKernelGGL((decode_kernel<E, 4, PG>), g, dim3(kThreads), 0, st, p); break;
+    case 1: hipLaunchKernelGGL((decode_kernel<E, 1, PG, C>), g, dim3(kThreads), 0, st, p); break;
+    case 2: hipLaunchKernelGGL((decode_kernel<E, 2, PG, C>), g, dim3(kThreads), 0, st, p); break;
+    case 3: hipLaunchKernelGGL((decode_kernel<E, 3, PG, C>), g, dim3(kThreads), 0, st, p); break;
+    case 4: hipLaunchKernelGGL((decode_kernel<E, 4, PG, C>), g, dim3(kThreads), 0, st, p); break;
     default: return -2;
   }
   return (int)hipGetLastError();
@@ -410,6 +499,18 @@ int launch_decode(int dtype, const DecodeParams& p, hipStream_t st) {
     case 0: return p.pg.tbl ? decode_launch<__bf16, true>(p, st) : decode_launch<__bf16, false>(p, st);
     case 1: return p.pg.tbl ? decode_launch<_Float16, true>(p, st) : decode_launch<_Float16, false>(p, st);
     case 2: return p.pg.tbl ? decode_launch<float, true>(p, st) : decode_launch<float, false>(p, st);
+  }
+  return -2;
+}
+
+// q / o in dtype, the cache rows fp8 (e4m3fn) with per-(row, head) scales: paged only
+int launch_decode_f8(int dtype, const DecodeParams& p, hipStream_t st) {
+  if ((int64_t)p.B * p.H == 0) return 0;
+  if (!p.pg.tbl || !p.kvs) return -2;
+  switch (dtype) {
+    case 0: return decode_launch<__bf16, true, f8e4>(p, st);
+    case 1: return decode_launch<_Float16, true, f8e4>(p, st);
+    case 2: return decode_launch<float, true, f8e4>(p, st);
   }
   return -2;
 }

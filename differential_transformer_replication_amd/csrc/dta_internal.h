@@ -135,9 +135,27 @@ struct DecodeParams {
   const int* Ldev;     // optional device length
   int Lsb;             // batch stride of Ldev: 0 = one length for the launch, 1 = int32 [B] (ragged)
   PageTable pg;        // paged launch: k / v are the page pool, ldw = max_pages * page size
+  // fp8 cache (dta_attn_decode_paged_fp8; NULL otherwise): k / v are pools of e4m3fn bytes (strides
+  // in bytes) and kvs the fp32 scales [page][row < P][h][N + 1] (index N: V), kvs_sb floats per page
+  const float* kvs;
+  int64_t kvs_sb;
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
+int launch_decode_f8(int dtype, const DecodeParams& p, hipStream_t st);   // dtype: q / o; cache rows fp8
+
+// dta_kv_quant_rows (kv_quant.hip): rows of K_i / V in the activation dtype -> e4m3fn bytes + scales
+struct KvQuantParams {
+  T5 ksrc, vsrc;       // [b][t][h][i][d] / [b][t][h][e], activation dtype, element strides
+  T5 kdst, vdst;       // byte pools [page][row < P][h][i][d] / [page][row < P][h][e], byte strides
+  float* kvs;          // scale pool [page][row < P][h][N + 1]
+  int64_t kvs_sb;      // floats per scale page
+  const int* slot;     // device int32 [B * Tn]: page * P + row, clamped to [0, slots - 1]
+  int B, Tn, H, N, HS, DV;
+  int shift;           // log2(page size)
+  int slots;           // (n_pages + 1) * P: the pool's pages and the spare page after them
+};
+int launch_kv_quant(int dtype, const KvQuantParams& p, hipStream_t st);
 
 struct ExtendParams {
   T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid

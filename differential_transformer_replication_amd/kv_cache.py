@@ -46,6 +46,9 @@ B x block_size rows; ``release`` hands a finished sequence's pages to the next p
 which ``prefill_paged`` adds to the live cache; ``fork`` lets several continuations of
 one prompt share its pages (copy on write).  The allocator lives on the host; the step
 is eager, stays within one window, and no existing path enters it.
+``PagedKVCache(..., kv_dtype="fp8_e4m3")`` keeps the pages as OCP e4m3fn bytes with one
+fp32 scale per (row, head, K_i | V): a step quantises its new rows (``ops.kv_quant_rows``)
+and decodes on the bytes (``ops.diff_attention_decode_paged_fp8``).
 """
 from __future__ import annotations
 
@@ -673,10 +676,20 @@ class PagedKVCache(KVCache):
     ``host_lengths`` an upper bound (``host_exact`` False) until ``sync()``; pages are then
     taken for the bound and ``sync()`` / ``release`` return the surplus."""
 
-    def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None):
+    KV_DTYPES = (None, "fp8_e4m3")
+
+    def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None):
         super().__init__()
         if page_size not in ops.PAGE_SIZES:
             raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
+        if kv_dtype not in self.KV_DTYPES:
+            raise ValueError(f"kv_dtype {kv_dtype!r} is not one of {self.KV_DTYPES}")
+        # "fp8_e4m3": the per-layer pool is uint8 (num_pages + 1, P, W), OCP e4m3fn bytes in the same
+        # row layout, next to scale_pool fp32 (num_pages + 1, P, H * (N + 1)): one scale per (row,
+        # head, K_i | V).  A step quantises its new rows (ops.kv_quant_rows) and decodes on the bytes
+        # (ops.diff_attention_decode_paged_fp8).  None: the pool in the projection's dtype.
+        self.kv_dtype = kv_dtype
+        self.scale_pool: Dict[int, torch.Tensor] = {}
         if num_pages < 1:
             raise ValueError("num_pages must be >= 1")
         self.use_graph = False                     # the paged step runs eagerly
@@ -708,6 +721,20 @@ class PagedKVCache(KVCache):
             buf = torch.empty(shape, device=like.device, dtype=like.dtype)
             self.pool[layer] = buf
         return buf
+
+    def layer_pool_fp8(self, layer: int, width: int, H: int, N: int, device):
+        """The layer's byte pool and scale pool (``kv_dtype="fp8_e4m3"``), made on first use."""
+        buf, sc = self.pool.get(layer), self.scale_pool.get(layer)
+        shape, sshape = (self.num_pages + 1, self.page_size, width), (self.num_pages + 1, self.page_size, H * (N + 1))
+        if buf is None or buf.shape != shape or buf.dtype != torch.uint8 or sc is None or sc.shape != sshape:
+            buf = torch.empty(shape, device=device, dtype=torch.uint8)
+            sc = torch.empty(sshape, device=device, dtype=torch.float32)
+            self.pool[layer], self.scale_pool[layer] = buf, sc
+        return buf, sc
+
+    def cache_bytes(self) -> int:
+        """Bytes the pools of every layer hold (spare pages included)."""
+        return sum(t.numel() * t.element_size() for d in (self.pool, self.scale_pool) for t in d.values())
 
     def _ensure(self, block_size: int, device) -> None:
         if self.block_table is None:
@@ -781,7 +808,7 @@ class PagedKVCache(KVCache):
                 self.pages[q].append(new)
             self._dirty_rows.add(q)
         if src:
-            for buf in self.pool.values():
+            for buf in list(self.pool.values()) + list(self.scale_pool.values()):    # fp8: bytes and their scales
                 buf.index_copy_(0, torch.tensor(dst, device=buf.device),
                                 buf.index_select(0, torch.tensor(src, device=buf.device)))
 
@@ -880,6 +907,9 @@ def _paged_attention_step(block, x, layer: int, cache: PagedKVCache, tbl, pos, c
         consts = _constants(attn, layer, H, hs, bs, x.device)
         cache.consts[layer] = consts
     weight, coef, freqs = consts
+    if cache.kv_dtype is not None:
+        return _paged_attention_step_fp8(attn, x, layer, cache, tbl, pos, counts, rows, one_row,
+                                         (H, N, hs, dv, bs), weight, coef, freqs)
     qkv = F.linear(x, weight)
     B, Tn, W = qkv.shape
     nq = H * N * hs
@@ -921,6 +951,63 @@ def _paged_attention_step(block, x, layer: int, cache: PagedKVCache, tbl, pos, c
             zero = torch.zeros_like(pos)
             out = torch.stack([ops.diff_attention_decode_paged(q[:, i], k_pool, v_pool, coef, tbl,
                                                                torch.where(counts > i, pos + (i + 1), zero))
+                               for i in range(Tn)], dim=1)
+    if hasattr(attn, "group_norm"):
+        gn = attn.group_norm
+        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
+    return attn.dropout(attn.proj(out))
+
+
+def _paged_attention_step_fp8(attn, x, layer: int, cache: PagedKVCache, tbl, pos, counts, rows, one_row: bool,
+                              spec, weight, coef, freqs):
+    """``_paged_attention_step`` on an fp8 pool (``kv_dtype="fp8_e4m3"``).  The prefill's
+    attention runs the fused training forward on the unquantised activations; every step
+    writes its new rows through ``ops.kv_quant_rows`` (straight from the RoPE temporary and
+    the V slice of ``qkv``: no concatenated copy); a one-row step runs
+    ``ops.diff_attention_decode_paged_fp8``, a multi-row step one such decode per row (there
+    is no fp8 extend kernel)."""
+    H, N, hs, dv, bs = spec
+    qkv = F.linear(x, weight)
+    B, Tn, W = qkv.shape
+    nq = H * N * hs
+    P, npg = cache.page_size, cache.num_pages
+    pool, scales = cache.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
+    r = torch.arange(Tn, device=qkv.device)
+    q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
+    k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
+    v_new = qkv[..., 2 * nq:].unflatten(-1, (H, dv))
+    if pos is None:
+        out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
+        if freqs is not None:
+            k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+            ops.rope_rows(k_new, k_rot, freqs[:Tn])
+            k_new = k_rot
+        at = r[None, :].expand(B, Tn)
+    else:
+        if freqs is not None:
+            tab = freqs[rows.flatten()]
+            q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+            k_rot = torch.empty_like(q_rot)
+            ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
+            ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
+            q, k_new = q_rot, k_rot
+        at = pos[:, None].long() + r[None, :]
+    real = (r[None, :] < counts[:, None]) & (at < bs)
+    page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
+    slots = (page * P + at % P).to(torch.int32).flatten()
+    k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
+    v_all = pool[..., nq:].unflatten(-1, (H, dv))
+    s_all = scales.unflatten(-1, (H, N + 1))
+    ops.kv_quant_rows(k_new, v_new, k_all, v_all, s_all, slots)
+    if pos is not None:
+        k_pool, v_pool, s_pool = k_all[:npg], v_all[:npg], s_all[:npg]
+        if one_row:
+            out = ops.diff_attention_decode_paged_fp8(q[:, 0], k_pool, v_pool, s_pool, coef, tbl,
+                                                      pos + counts).view(B, 1, H * dv)
+        else:
+            zero = torch.zeros_like(pos)
+            out = torch.stack([ops.diff_attention_decode_paged_fp8(q[:, i], k_pool, v_pool, s_pool, coef, tbl,
+                                                                   torch.where(counts > i, pos + (i + 1), zero))
                                for i in range(Tn)], dim=1)
     if hasattr(attn, "group_norm"):
         gn = attn.group_norm
@@ -1089,7 +1176,7 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
 
 @torch.no_grad()
 def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
-                   n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64):
+                   n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1099,7 +1186,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     so its samples share the prompt's full pages (a partial last page is copied when a
     sample first writes into it); the batch is sample-major within a prompt, and the
     result is a list of B lists of ``n_samples`` tensors.  ``num_pages``: the pool size;
-    default the exact need of the call (``OutOfPages`` if a given one is too small)."""
+    default the exact need of the call (``OutOfPages`` if a given one is too small).
+    ``kv_dtype``: ``PagedKVCache``'s (``"fp8_e4m3"``: the pages hold e4m3fn bytes and scales)."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1114,7 +1202,7 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
             shared = n // page_size if end > n else -(-n // page_size)         # nothing written: all pages shared
             num_pages += shared + n_samples * (-(-end // page_size) - shared)
         num_pages = max(num_pages, 1)
-    cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1))
+    cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype)
     roots, logits = prefill_paged(model, prompts, cache)
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]

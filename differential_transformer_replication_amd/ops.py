@@ -953,3 +953,145 @@ def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
                              P, max_pages, n_pages, block_table.data_ptr())
     _lib.check(lib.dta_attn_extend_paged(a, _lib.stream_handle(q.device)))
     return o.view(B, Tq, H * dv)
+
+
+# --------------------------------------------------------------- fp8 pages ---
+# The paged cache with one byte per element (include/diffattn.h "FP8 paged KV cache"):
+# OCP e4m3fn bytes in today's row layout [K (H, N, hs) | V (H, dv)] and one fp32 scale per
+# (row, head, K_i | V) in scale_pool (n_pages, P, H, N + 1), index N holding V's scale.
+FP8_MAX = 448.0
+
+
+def fp8_cache_supported() -> bool:
+    """Whether the loaded library has the fp8-cache entry points (an older build of the
+    same ABI may not)."""
+    return _lib.fp8_symbols(_lib.load())
+
+
+def kv_quant_reference(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """The cache's quantiser in plain torch (any device), over the last dimension of ``x``:
+    amax = max|x| in fp32 of the values as stored, scale = amax / 448, byte =
+    e4m3fn_rne(clamp(x / scale, -448, 448)); a zero vector gives scale 0 and bytes 0.  The
+    clamp precedes the conversion (torch's own conversion turns 500.0 into NaN).
+    Returns (uint8 bytes shaped like ``x``, fp32 scales shaped like ``x[..., 0]``)."""
+    xf = x.detach().to(torch.float32)
+    amax = xf.abs().amax(dim=-1)
+    scale = amax / FP8_MAX
+    safe = torch.where(amax > 0, scale, torch.ones_like(scale))
+    y = (xf / safe[..., None]).clamp_(-FP8_MAX, FP8_MAX)
+    y = torch.where(amax[..., None] > 0, y, torch.zeros_like(y))
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def kv_dequant_reference(k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor, table_row, length: int):
+    """Rows 0 .. length-1 of one sequence, gathered through its block-table row and
+    dequantised (x^ = float(byte) * scale) in plain torch on the pools' device.
+    k_pool_u8 (n_pages, P, H, N, hs), v_pool_u8 (n_pages, P, H, dv), scale_pool (n_pages, P,
+    H, N + 1); ``table_row``: the sequence's page ids (a tensor or a list; entries past
+    ceil(length / P) are not looked at).  Returns fp32 (k (length, H, N, hs), v (length, H, dv))."""
+    P = k_pool_u8.shape[1]
+    n = -(-int(length) // P)
+    pages = torch.as_tensor(table_row)[:n].to(device=k_pool_u8.device, dtype=torch.long)
+    k = k_pool_u8.index_select(0, pages).flatten(0, 1)[:length].contiguous().view(torch.float8_e4m3fn).float()
+    v = v_pool_u8.index_select(0, pages).flatten(0, 1)[:length].contiguous().view(torch.float8_e4m3fn).float()
+    s = scale_pool.index_select(0, pages).flatten(0, 1)[:length].float()
+    N = k.shape[2]
+    return k * s[..., :N, None], v * s[..., N, None]
+
+
+def _fp8_views(k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor):
+    """Checks of the three fp8 pool views; returns (n_pages, P, H, N, hs, dv)."""
+    if k_pool_u8.dim() != 5 or v_pool_u8.dim() != 4 or scale_pool.dim() != 4:
+        raise RuntimeError("k_pool_u8 must be (n_pages, P, H, N, hs), v_pool_u8 (n_pages, P, H, dv) and "
+                           "scale_pool (n_pages, P, H, N + 1)")
+    n_pages, P, H, N, hs = k_pool_u8.shape
+    dv = v_pool_u8.shape[-1]
+    if k_pool_u8.dtype != torch.uint8 or v_pool_u8.dtype != torch.uint8 or scale_pool.dtype != torch.float32:
+        raise RuntimeError("the fp8 pools are uint8 views and the scale pool is fp32")
+    if P not in PAGE_SIZES:
+        raise RuntimeError(f"page size {P} is not one of {PAGE_SIZES}")
+    if n_pages < 1:
+        raise RuntimeError("the pool holds no page")
+    if tuple(v_pool_u8.shape) != (n_pages, P, H, dv) or tuple(scale_pool.shape) != (n_pages, P, H, N + 1):
+        raise RuntimeError("v_pool_u8 / scale_pool shapes do not match k_pool_u8")
+    if scale_pool.stride()[1:] != (H * (N + 1), N + 1, 1):
+        raise RuntimeError("the scales of a page must be contiguous")
+    if k_pool_u8.device != v_pool_u8.device or k_pool_u8.device != scale_pool.device:
+        raise RuntimeError("the pools must share a device")
+    return n_pages, P, H, N, hs, dv
+
+
+def diff_attention_decode_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
+                                    coef: Tensor, block_table: Tensor, lengths: Tensor,
+                                    max_length: Optional[int] = None) -> Tensor:
+    """``diff_attention_decode_paged`` over an fp8 page pool: the kernel reads e4m3fn bytes
+    and their scales and never materialises the dequantised rows; every sum is fp32.
+
+    q: (B, H, N, hs) bf16 / f16 / f32 (the dtype of the result); k_pool_u8 (n_pages, P, H, N,
+    hs) and v_pool_u8 (n_pages, P, H, dv): uint8 views of one packed byte pool; scale_pool
+    (n_pages, P, H, N + 1) fp32, contiguous inside a page.  ``block_table``, ``lengths``,
+    ``max_length``, clamps, zeros for an empty sequence: as ``diff_attention_decode_paged``;
+    rows past a length and pages nobody names may hold any bytes and any scales, NaN and
+    Inf included.  Returns (B, H*dv).  No fallback: raises if the library lacks the entry
+    point (``fp8_cache_supported``)."""
+    lib = _lib.load()
+    if not _lib.fp8_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no fp8-cache entry points (fp8_cache_supported)")
+    _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
+    B, H, N, hs = q.shape
+    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
+    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
+        raise RuntimeError("the pool views do not match q")
+    if (not isinstance(block_table, Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != q.device):
+        raise RuntimeError(f"block_table must be a device int32 tensor of shape ({B}, max_pages) on {q.device}")
+    if not block_table.is_contiguous():
+        raise RuntimeError("block_table must be contiguous")
+    max_pages = block_table.shape[1]
+    T_cap = max_pages * P
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    _batch_int32(lengths, B, q, "lengths")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
+    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    a = _lib.DecodePagedFp8Args(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
+                                _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_pool_u8), _lib.tensor5(v_pool_u8),
+                                _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr(),
+                                P, max_pages, n_pages, block_table.data_ptr(),
+                                scale_pool.data_ptr(), scale_pool.stride(0))
+    _lib.check(lib.dta_attn_decode_paged_fp8(a, _lib.stream_handle(q.device)))
+    return o.view(B, H * dv)
+
+
+def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
+                  slots: Tensor) -> None:
+    """Quantise the new rows of a step into an fp8 page pool (``kv_quant_reference``'s
+    arithmetic, one launch): k_new (B, Tn, H, N, hs) and v_new (B, Tn, H, dv) are strided
+    views in the activation dtype (K may be the RoPE temporary, V a slice of the packed
+    projection); row (b, t) goes to row ``slots[b * Tn + t] % P`` of page ``slots[..] // P``.
+    The pool views hold the pool's pages and, last, the spare page the padding rows of a
+    step point into; ``slots``: contiguous device int32 (B * Tn,), clamped into the views by
+    the kernel.  Writes the bytes and the N + 1 scales of the named rows, nothing else.
+    hs and dv must be multiples of 16 (``RuntimeError`` otherwise: there is no fallback)."""
+    lib = _lib.load()
+    if not _lib.fp8_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no fp8-cache entry points (fp8_cache_supported)")
+    _require_gpu(k_new, v_new, k_pool_u8, v_pool_u8, scale_pool, slots)
+    if k_new.dim() != 5 or v_new.dim() != 4:
+        raise RuntimeError("k_new must be (B, Tn, H, N, hs) and v_new (B, Tn, H, dv)")
+    B, Tn, H, N, hs = k_new.shape
+    n_all, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
+    if (Hp, Np, hsp) != (H, N, hs) or tuple(v_new.shape) != (B, Tn, H, dv) or k_new.dtype != v_new.dtype:
+        raise RuntimeError("k_new / v_new do not match each other or the pool views")
+    if n_all < 2:
+        raise RuntimeError("the pool views must hold at least one page and the spare page")
+    if (slots.dtype != torch.int32 or tuple(slots.shape) != (B * Tn,) or not slots.is_contiguous()
+            or slots.device != k_new.device or k_pool_u8.device != k_new.device):
+        raise RuntimeError(f"slots must be a contiguous device int32 tensor of shape ({B * Tn},) on {k_new.device}")
+    a = _lib.KvQuantRowsArgs(_lib.dtype_code(k_new.dtype), B, Tn, H, N, hs, dv, P, n_all - 1,
+                             _lib.tensor5(k_new), _lib.tensor5(v_new), _lib.tensor5(k_pool_u8),
+                             _lib.tensor5(v_pool_u8), scale_pool.data_ptr(), scale_pool.stride(0), slots.data_ptr())
+    _lib.check(lib.dta_kv_quant_rows(a, _lib.stream_handle(k_new.device)))

@@ -49,6 +49,8 @@ extern "C" {
                                   presence of the symbols is the capability check (dlsym / hasattr);
                                   still 9, added the same way: dta_attn_decode_paged, dta_attn_extend_paged
                                   (block-table KV cache over a pool of pages);
+                                  still 9, added the same way: dta_attn_decode_paged_fp8, dta_kv_quant_rows
+                                  (e4m3fn pages with per-(row, head) scales);
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -438,6 +440,81 @@ typedef struct dta_attn_extend_paged_args {
   const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
 } dta_attn_extend_paged_args;
 int dta_attn_extend_paged(const dta_attn_extend_paged_args* a, void* stream);
+
+/* FP8 paged KV cache (still ABI 9; the presence of the two symbols is the capability
+ * check): the page pool holds one byte per element and a decode step reads
+ * N*hs + dv + 4*(N+1) bytes per (row, head) instead of 2*(N*hs + dv).
+ * Format:
+ *   elements  OCP e4m3fn (gfx950's native fp8, torch.float8_e4m3fn; not fnuz)
+ *   scales    fp32, one per (cache row, head, branch i) for K_i and one per (cache row,
+ *             head) for V: scale_pool [page][row < P][h][N+1], contiguous inside a page,
+ *             index N holding V's scale; scale_page_stride (floats) >= P * H * (N+1)
+ *   k_pool / v_pool   today's row layout [K (H, N, hs) | V (H, dv)], one byte per element,
+ *             described by dta_tensor with strides in elements = bytes
+ *   quantisation of one vector x (a K_i head row of hs values, a V head row of dv values):
+ *             amax = max|x| (fp32, of the values as the activation dtype stores them),
+ *             scale = amax / 448, byte = e4m3_rne(clamp(x / scale, -448, 448)); the clamp is
+ *             explicit and precedes the conversion; amax == 0 gives scale 0 and bytes 0 with
+ *             no division; non-finite input is undefined, as in the 16-bit cache
+ *   dequantisation    x^ = float(byte) * scale, never materialised in memory
+ *
+ * dta_attn_decode_paged_fp8 replaces the lines dta_attn_decode_paged does (the per-token
+ * full-prefix recompute of generate(), diff_transformer.py:177-185; Ndiff_transformer.py
+ * generate; control.py:163-171) on such a pool:
+ *   o[b] = sum_i coef[h][i] * softmax(q_i[b] . K^_i(b, 0:len_b)^T * scale) V^(b, 0:len_b)
+ * dtype is the dtype of q and o.  The dot product of a K row is multiplied by its scale
+ * once per (row, branch); V's scale is folded into the probability before the V
+ * accumulation and the row sum uses the unscaled probability; all sums are fp32.  Plans,
+ * chunk choice from t_cap, workspace (dta_attn_decode_workspace_bytes), the clamps of
+ * len_b and of every page id, the early exit of a chunk past len_b (before any load, scale
+ * loads included) and zeros for len_b == 0 are dta_attn_decode_paged's.  Rows >= len_b and
+ * unowned pages may hold any bytes and any scales, NaN and Inf included.
+ * Errors: everything dta_attn_decode_paged rejects (the pool views are checked as byte
+ * views), and DTA_ERR_INVALID for a null or not 4-byte aligned scale_pool_dev, a
+ * scale_page_stride below P * H * (N+1), or a byte-pool row or page stride that is not a
+ * multiple of 16. */
+typedef struct dta_attn_decode_paged_fp8_args {
+  int32_t dtype;             /* of q and o */
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t length;            /* host upper bound of every lengths_dev[b] (<= t_cap); sizes the grid */
+  int32_t t_cap;             /* = max_pages * page_size; workspace row length */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;   /* k_pool / v_pool: e4m3fn bytes, strides in bytes */
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* lengths_dev;/* device int32 [B], required: valid cached keys of sequence b */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+  const float* scale_pool_dev;     /* fp32 [page][row < P][h][N+1] */
+  int64_t scale_page_stride;       /* floats from one page's scales to the next */
+} dta_attn_decode_paged_fp8_args;
+int dta_attn_decode_paged_fp8(const dta_attn_decode_paged_fp8_args* a, void* stream);
+
+/* The write side: quantise a step's new rows into the pool.  Replaces, for an fp8 pool,
+ * the scatter of the new K_i / V rows into the cache (the index_put_ of
+ * kv_cache._paged_attention_step; in the reference those rows are recomputed per token,
+ * diff_transformer.py:177-185).  k_new [b][t < Tn][h][i][d] and v_new [b][t < Tn][h][e] are
+ * strided views in the activation dtype (16-byte aligned, strides multiples of 16 bytes;
+ * K may be the RoPE temporary, V a slice of the packed projection).  slot_dev: device int32
+ * [B * Tn], slot = page * page_size + row of row (b, t); padding rows point into the spare
+ * page, page n_pages: the pool views and the scale pool hold n_pages + 1 pages.  Every slot
+ * is clamped to [0, (n_pages + 1) * page_size - 1] before it forms an address.  Writes the
+ * bytes and the N+1 scales of every (row, head) in the format above and nothing else.
+ * DTA_ERR_UNSUPPORTED: head_size or dv not a multiple of 16 (or above 128 / 256), n_terms
+ * outside 1..4.  DTA_ERR_INVALID: a page_size outside {32, 64, 128, 256}, n_pages < 1, a
+ * null or misaligned pointer or stride, a scale_page_stride below P * H * (N+1).
+ * B * Tn == 0: DTA_OK, no launch. */
+typedef struct dta_kv_quant_rows_args {
+  int32_t dtype;             /* of k_new and v_new */
+  int32_t B, Tn, H, n_terms, head_size, dv;
+  int32_t page_size, n_pages;
+  dta_tensor k_new, v_new;
+  dta_tensor k_pool, v_pool; /* e4m3fn bytes, strides in bytes, n_pages + 1 pages */
+  float* scale_pool_dev;     /* fp32 [page][row < P][h][N+1], n_pages + 1 pages */
+  int64_t scale_page_stride;
+  const int32_t* slot_dev;   /* device int32 [B * Tn] */
+} dta_kv_quant_rows_args;
+int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream);
 
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
