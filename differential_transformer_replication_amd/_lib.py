@@ -104,57 +104,42 @@ class RopeArgs(ctypes.Structure):
                 ("src", DtaTensor), ("dst", DtaTensor), ("freqs", ctypes.c_void_p)]
 
 
+def _cache_op_fields(sizes, k: str, v: str, pointers):
+    """The field list the decode and extend structs share: dtype .. dv, the op's own int32
+    ``sizes``, scale, the four views (the cache's named ``k`` / ``v``), coef, the op's ``pointers``."""
+    i32 = ("dtype", "B", "H", "n_terms", "head_size", "dv") + sizes
+    return ([(n, ctypes.c_int32) for n in i32] + [("scale", ctypes.c_float)]
+            + [(n, DtaTensor) for n in ("q", k, v, "o")]
+            + [(n, ctypes.c_void_p) for n in ("coef",) + pointers])
+
+
+_PAGED_FIELDS = [("page_size", ctypes.c_int32), ("max_pages", ctypes.c_int32), ("n_pages", ctypes.c_int32),
+                 ("block_table_dev", ctypes.c_void_p)]
+_DECODE_SIZES = ("length", "t_cap")
+
+
 class DecodeArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("length", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_cache", DtaTensor), ("v_cache", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("length_dev", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(_DECODE_SIZES, "k_cache", "v_cache", ("workspace", "length_dev"))
 
 
 class ExtendArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("Tq", ctypes.c_int32), ("pos", ctypes.c_int32), ("t_cap", ctypes.c_int32),
-                ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_cache", DtaTensor), ("v_cache", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(("Tq", "pos", "t_cap"), "k_cache", "v_cache", ())
 
 
 class DecodeRaggedArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("length", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_cache", DtaTensor), ("v_cache", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("lengths_dev", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(_DECODE_SIZES, "k_cache", "v_cache", ("workspace", "lengths_dev"))
 
 
 class ExtendRaggedArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("Tq", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_cache", DtaTensor), ("v_cache", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p), ("pos_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(("Tq", "t_cap"), "k_cache", "v_cache", ("pos_dev", "count_dev"))
 
 
 class DecodePagedArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("length", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_pool", DtaTensor), ("v_pool", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("lengths_dev", ctypes.c_void_p),
-                ("page_size", ctypes.c_int32), ("max_pages", ctypes.c_int32), ("n_pages", ctypes.c_int32),
-                ("block_table_dev", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(_DECODE_SIZES, "k_pool", "v_pool", ("workspace", "lengths_dev")) + _PAGED_FIELDS
 
 
 class ExtendPagedArgs(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
-                ("Tq", ctypes.c_int32), ("t_cap", ctypes.c_int32), ("scale", ctypes.c_float),
-                ("q", DtaTensor), ("k_pool", DtaTensor), ("v_pool", DtaTensor), ("o", DtaTensor),
-                ("coef", ctypes.c_void_p), ("pos_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p),
-                ("page_size", ctypes.c_int32), ("max_pages", ctypes.c_int32), ("n_pages", ctypes.c_int32),
-                ("block_table_dev", ctypes.c_void_p)]
+    _fields_ = _cache_op_fields(("Tq", "t_cap"), "k_pool", "v_pool", ("pos_dev", "count_dev")) + _PAGED_FIELDS
 
 
 class DecodePagedFp8Args(ctypes.Structure):

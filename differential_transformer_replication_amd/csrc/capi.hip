@@ -484,21 +484,24 @@ size_t dta_attn_decode_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, in
   return single > split ? single : split;
 }
 
-// dta_attn_decode and dta_attn_decode_ragged: one validation, one launch path.  ldev / lsb:
-// the device length(s) and their batch stride (0: one value, 1: int32 [B]).
+// log2 of a page size the kernels take (32, 64, 128, 256), or 0 for any other
+static int page_shift(int page_size) {
+  switch (page_size) {
+    case 32: return 5;
+    case 64: return 6;
+    case 128: return 7;
+    case 256: return 8;
+    default: return 0;
+  }
+}
+
 // The paged entry points' own arguments: a block table over a pool of n_pages pages of
 // page_size rows, max_pages entries per sequence, t_cap the logical capacity.
 extern "C++" template <class A>
 static bool page_table(const A* a, PageTable& g) {
   if (!a->block_table_dev || (uintptr_t)a->block_table_dev % 4) return false;
-  int shift = 0;
-  switch (a->page_size) {
-    case 32: shift = 5; break;
-    case 64: shift = 6; break;
-    case 128: shift = 7; break;
-    case 256: shift = 8; break;
-    default: return false;
-  }
+  const int shift = page_shift(a->page_size);
+  if (!shift) return false;
   if (a->n_pages < 1 || a->max_pages < 1 || (int64_t)a->max_pages * a->page_size != a->t_cap) return false;
   g = PageTable{a->block_table_dev, a->max_pages, shift, a->n_pages};
   return true;
@@ -512,6 +515,8 @@ static bool ok_byte_pool(const dta_tensor& t, int width, bool with_i) {
   return t.sb >= 0 && t.st >= 0 && t.sh >= 0 && t.si >= 0;
 }
 
+// dta_attn_decode and dta_attn_decode_ragged: one validation, one launch path.  ldev / lsb:
+// the device length(s) and their batch stride (0: one value, 1: int32 [B]).
 // kc / vc: the cache views (contiguous [b][t], or with a table in pg the page pool);
 // scales: NULL, or the fp32 scale pool of an fp8 page pool (kc / vc are then byte views)
 extern "C++" template <class A>
@@ -571,14 +576,8 @@ int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream) {
   if (!a || !ok_dims(a->dtype, a->B, a->Tn, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (a->head_size % 16 || a->dv % 16 || a->head_size > 128 || a->dv > 256 || a->n_terms > 4)
     return DTA_ERR_UNSUPPORTED;
-  int shift = 0;
-  switch (a->page_size) {
-    case 32: shift = 5; break;
-    case 64: shift = 6; break;
-    case 128: shift = 7; break;
-    case 256: shift = 8; break;
-    default: return DTA_ERR_INVALID;
-  }
+  const int shift = page_shift(a->page_size);
+  if (!shift) return DTA_ERR_INVALID;
   if (a->n_pages < 1 || ((int64_t)a->n_pages + 1) * a->page_size > INT32_MAX) return DTA_ERR_INVALID;
   if (!a->slot_dev || (uintptr_t)a->slot_dev % 4 || !a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4 ||
       a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))

@@ -29,26 +29,19 @@ a tool result, the scoring of candidate tokens with ``all_rows=True``), through
 prefills a long prompt in bounded memory (``prefill_chunk``): the first chunk runs
 the fused training forward, every further chunk appends.
 
-Everything above keeps the whole batch at one position (``KVCache.length``).  The
-ragged path next to it (``RaggedKVCache``, ``prefill_ragged``, ``decode_ragged``,
-``append_ragged``, ``generate_ragged``) keeps one length per sequence on the device,
-read there by ``ops.diff_attention_decode_ragged`` / ``ops.diff_attention_extend_ragged``:
-prompts of different lengths generate as one batch, a verification step accepts a
-different number of tokens per sequence (``RaggedKVCache.truncate`` rolls the rest
-back), and a sequence may sit at position 0 while the others are far along.  It runs
-eagerly and within one window; no existing path enters it.
-
-The paged path (``PagedKVCache``, ``prefill_paged``, ``decode_paged``, ``append_paged``,
-``generate_paged``) stores the same rows in a shared pool of fixed-size pages, reached by
-the kernels through a per-sequence block table (``ops.diff_attention_decode_paged`` /
-``ops.diff_attention_extend_paged``): a batch holds the pages its lengths need, not
-B x block_size rows; ``release`` hands a finished sequence's pages to the next prompt,
-which ``prefill_paged`` adds to the live cache; ``fork`` lets several continuations of
-one prompt share its pages (copy on write).  The allocator lives on the host; the step
-is eager, stays within one window, and no existing path enters it.
-``PagedKVCache(..., kv_dtype="fp8_e4m3")`` keeps the pages as OCP e4m3fn bytes with one
-fp32 scale per (row, head, K_i | V): a step quantises its new rows (``ops.kv_quant_rows``)
-and decodes on the bytes (``ops.diff_attention_decode_paged_fp8``).
+Everything above keeps the whole batch at one position (``KVCache.length``).  Two further
+caches keep one length per sequence on the device; they run eagerly, stay within one
+window, and no existing path enters them.  ``RaggedKVCache`` (``prefill_ragged``,
+``decode_ragged``, ``append_ragged``, ``generate_ragged``) has the same contiguous rows:
+prompts of different lengths generate as one batch, a verification step accepts a different
+number of tokens per sequence (``truncate`` rolls the rest back).  ``PagedKVCache``
+(``prefill_paged``, ``decode_paged``, ``append_paged``, ``generate_paged``) keeps the rows in a
+shared pool of fixed-size pages behind a per-sequence block table, with a host allocator:
+``release`` hands a finished sequence's pages to the next prompt, ``fork`` shares a prompt's
+pages among its continuations (copy on write); ``kv_dtype="fp8_e4m3"`` stores e4m3fn bytes
+with one fp32 scale per (row, head, K_i | V).  Both run one step (``_seq_model_step``,
+``_seq_attention_step``); the cache says where the new rows go (``write_rows``) and which op
+reads them back (``decode_rows``, ``extend_rows``).
 """
 from __future__ import annotations
 
@@ -91,6 +84,7 @@ class KVCache:
         self.consts: Dict[int, tuple] = {}
         self.graph = None
         self.use_graph = os.environ.get("DTA_DECODE_GRAPH", "1") != "0"
+        self.kv_dtype = None                       # rows in the projection's dtype (PagedKVCache may differ)
 
     def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
         buf = self.rows.get(layer)
@@ -110,15 +104,23 @@ def _spec(block):
     return a, a.num_heads, 1, a.head_size, a.head_size, a.heads[0].block_size
 
 
-def _constants(attn, layer: int, H: int, hs: int, bs: int, device):
-    freqs = None
-    if hasattr(attn.heads[0], "freqs_cis"):
-        from .Ndiff_transformer import rope_table
-        freqs = rope_table(attn.heads[0].freqs_cis, bs, hs).to(device=device, dtype=torch.float32).contiguous()
-    if hasattr(attn, "coefficients"):
-        return attn.packed_weight(), attn.coefficients(layer), freqs
-    # control.py MultiHeadAttention: packed [Q | K | V], one branch of weight 1
-    return attn.packed_weight(), torch.ones(H, 1, device=device, dtype=torch.float32), freqs
+def _constants(cache: KVCache, attn, layer: int, H: int, hs: int, bs: int, x: torch.Tensor):
+    """(packed projection weight, branch coefficients, RoPE table or None) of a layer,
+    built on ``x``'s device on first use and kept in ``cache.consts``."""
+    consts = cache.consts.get(layer)
+    if consts is None:
+        device = x.device
+        freqs = None
+        if hasattr(attn.heads[0], "freqs_cis"):
+            from .Ndiff_transformer import rope_table
+            freqs = rope_table(attn.heads[0].freqs_cis, bs, hs).to(device=device, dtype=torch.float32).contiguous()
+        weight = attn.packed_weight()
+        if hasattr(attn, "coefficients"):
+            coef = attn.coefficients(layer)
+        else:   # control.py MultiHeadAttention: packed [Q | K | V], one branch of weight 1
+            coef = torch.ones(H, 1, device=device, dtype=torch.float32)
+        consts = cache.consts[layer] = (weight, coef, freqs)
+    return consts
 
 
 def _attention_step(block, x: torch.Tensor, layer: int, cache: KVCache, pos: int) -> torch.Tensor:
@@ -126,11 +128,7 @@ def _attention_step(block, x: torch.Tensor, layer: int, cache: KVCache, pos: int
     control.py's MultiHeadAttention) for the rows at positions pos .. pos+Tn-1,
     reading and extending the layer's cache."""
     attn, H, N, hs, dv, bs = _spec(block)
-    consts = cache.consts.get(layer)
-    if consts is None:
-        consts = _constants(attn, layer, H, hs, bs, x.device)
-        cache.consts[layer] = consts
-    weight, coef, freqs = consts
+    weight, coef, freqs = _constants(cache, attn, layer, H, hs, bs, x)
     rope = freqs is not None
     qkv = F.linear(x, weight)
     B, Tn, W = qkv.shape
@@ -171,18 +169,45 @@ def _attention_step(block, x: torch.Tensor, layer: int, cache: KVCache, pos: int
             v_rows[:, pos:pos + 1].copy_(v_new)
             out = ops.diff_attention_decode(q[:, 0], k_rows, v_rows, coef, pos + 1)
         out = out.view(B, 1, H * dv)
+    return _attention_tail(attn, out)
+
+
+def _attention_tail(attn, out: torch.Tensor) -> torch.Tensor:
+    """What follows the heads' concatenated output: the differential MHAs' GroupLayerNorm
+    with its constant scale, the output projection, dropout."""
     if hasattr(attn, "group_norm"):
         gn = attn.group_norm
         out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
     return attn.dropout(attn.proj(out))
 
 
+def _decode_per_row(decode, Tn: int, pos, counts=None) -> torch.Tensor:
+    """The multi-row step of a head size without an extend plan (40, 72: not a multiple of
+    16), or of an fp8 pool: ``decode(i, lengths)`` once per row i -- correct, but the cache
+    is read once per row.  ``pos``: a host integer, every row real; or with ``counts`` device
+    int32 (B,), a padding row decoding at length 0 (zeros)."""
+    if counts is None:
+        return torch.stack([decode(i, pos + i + 1) for i in range(Tn)], dim=1)
+    zero = torch.zeros_like(pos)
+    return torch.stack([decode(i, torch.where(counts > i, pos + (i + 1), zero)) for i in range(Tn)], dim=1)
+
+
+def _rope_rows_at(q, k_new, freqs, rows):
+    """``q`` and ``k_new`` (B, Tn, H, N, hs) rotated to the positions ``rows`` (B, Tn), into
+    temporaries: one table row per (b, r), so the views collapse to (1, B*Tn, ...)."""
+    B, Tn, H, N, hs = q.shape
+    tab = freqs[rows.flatten()]
+    q_rot = torch.empty(B, Tn, H, N, hs, device=q.device, dtype=q.dtype)
+    k_rot = torch.empty_like(q_rot)
+    ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
+    ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
+    return q_rot, k_rot
+
+
 def _extend_rows(qkv, buf, coef, freqs, H: int, N: int, hs: int, dv: int, pos: int) -> torch.Tensor:
     """Attention of the Tn new rows at positions pos .. pos+Tn-1 (pos > 0, host
     integer): their K_i / V rows go into the cache first, then one
-    ``diff_attention_extend`` launch; head sizes it has no plan for (40, 72: not a
-    multiple of 16) take one decode launch per row instead -- correct, but the cache
-    is read once per row."""
+    ``diff_attention_extend`` launch, or ``_decode_per_row`` where it has no plan."""
     B, Tn, _ = qkv.shape
     nq = H * N * hs
     q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
@@ -200,8 +225,7 @@ def _extend_rows(qkv, buf, coef, freqs, H: int, N: int, hs: int, dv: int, pos: i
     buf[:, pos:pos + Tn, nq:].copy_(qkv[..., 2 * nq:])
     if ops.extend_supported(qkv.dtype, hs, N, dv):
         return ops.diff_attention_extend(q, k_rows, v_rows, coef, pos)
-    rows = [ops.diff_attention_decode(q[:, r], k_rows, v_rows, coef, pos + r + 1) for r in range(Tn)]
-    return torch.stack(rows, dim=1)
+    return _decode_per_row(lambda i, n: ops.diff_attention_decode(q[:, i], k_rows, v_rows, coef, n), Tn, pos)
 
 
 class DevicePosition:
@@ -305,10 +329,7 @@ def append_logits(model, new_idx: torch.Tensor, cache: KVCache, all_rows: bool =
     for buf in cache.rows.values():
         if buf.shape[0] != new_idx.shape[0]:
             raise ValueError(f"batch size {new_idx.shape[0]} differs from the cache's {buf.shape[0]}")
-    if all_rows:
-        logits = _model_step(model, new_idx, cache, cache.length, all_rows=True)
-    else:
-        logits = _model_step(model, new_idx, cache, cache.length)
+    logits = _model_step(model, new_idx, cache, cache.length, all_rows=all_rows)
     cache.length += Tn
     if cache.length >= bs:
         cache.length = 0                      # a full window slides next step
@@ -383,6 +404,26 @@ class RaggedKVCache(KVCache):
             self.rows[layer] = buf[:, :cap]
         return self.rows[layer]
 
+    def write_rows(self, layer: int, qkv, k_rot, dims, bs: int, tbl, pos, counts):
+        """Scatter a step's new rows: the real ones to cache rows pos[b] + r, the padding to
+        the spare row.  Returns the (k_rows, v_rows) views the kernels read."""
+        H, N, hs, dv = dims
+        B, Tn, W = qkv.shape
+        nq = H * N * hs
+        buf = self.layer(layer, B, bs, W - nq, qkv)
+        r = torch.arange(Tn, device=qkv.device)
+        real = r[None, :] < counts[:, None]
+        dst = torch.where(real, pos[:, None].long() + r[None, :], bs).clamp_(max=bs)
+        self.store[layer].index_put_((torch.arange(B, device=qkv.device)[:, None].expand(B, Tn), dst),
+                                     _packed_new_rows(qkv, k_rot, nq))
+        return buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
+
+    def decode_rows(self, kv, q, coef, tbl, lengths):
+        return ops.diff_attention_decode_ragged(q, *kv, coef, lengths)
+
+    def extend_rows(self, kv, q, coef, tbl, pos, counts):
+        return ops.diff_attention_extend_ragged(q, *kv, coef, pos, counts)
+
     def set_lengths(self, lengths: Sequence[int], device) -> None:
         self.host_lengths = [int(n) for n in lengths]
         self.lengths = torch.tensor(self.host_lengths, dtype=torch.int32, device=device)
@@ -412,62 +453,53 @@ class RaggedKVCache(KVCache):
         self.set_lengths(new, self.lengths.device)
 
 
-def _ragged_attention_step(block, x, layer: int, cache: RaggedKVCache, pos, counts, rows, one_row: bool):
-    """``_attention_step`` for rows at per-sequence positions: sequence b's Tn rows sit
-    at pos[b] .. pos[b]+Tn-1, the first counts[b] of them real (pos, counts: device
-    int32 (B,); rows: their (B, Tn) long positions, clamped to the window).  The real
-    rows' K_i / V go to cache rows pos[b] + r, the padding rows' to the spare row."""
+def _packed_new_rows(qkv, k_rot, nq: int):
+    """A step's new cache rows ``[K | V]`` (B, Tn, W - nq): the slice of ``qkv``, or with
+    RoPE the rotated K_i next to its V."""
+    if k_rot is None:
+        return qkv[..., nq:]
+    return torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
+
+
+def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one_row: bool):
+    """``_attention_step`` for rows at per-sequence positions, on a ``RaggedKVCache``
+    (``tbl=None``) or a ``PagedKVCache`` (``tbl``: the step's contiguous (B, max_pages) table):
+    sequence b's Tn rows sit at pos[b] .. pos[b]+Tn-1, the first counts[b] of them real (pos,
+    counts: device int32 (B,); rows: their (B, Tn) long positions, clamped to the window).
+    The cache writes the new rows (``write_rows``: the padding rows land in its spare row or
+    page) and names the op that reads them back (``decode_rows``, ``extend_rows``).
+    ``pos=None``: the paged cache's right-padded prefill from position 0 (fused training
+    forward on the unquantised activations; counts = the prompt lengths)."""
     attn, H, N, hs, dv, bs = _spec(block)
-    consts = cache.consts.get(layer)
-    if consts is None:
-        consts = _constants(attn, layer, H, hs, bs, x.device)
-        cache.consts[layer] = consts
-    weight, coef, freqs = consts
+    weight, coef, freqs = _constants(cache, attn, layer, H, hs, bs, x)
     qkv = F.linear(x, weight)
-    B, Tn, W = qkv.shape
-    nq = H * N * hs
-    buf = cache.layer(layer, B, bs, W - nq, qkv)
-    store = cache.store[layer]
-    q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
-    new_rows = qkv[..., nq:]
-    if freqs is not None:
-        # one table row per (b, r): the (B, Tn, ...) views collapse to (1, B*Tn, ...)
-        tab = freqs[rows.flatten()]
-        k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
-        q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
-        k_rot = torch.empty_like(q_rot)
-        ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
-        ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
-        q = q_rot
-        new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
-    r = torch.arange(Tn, device=qkv.device)
-    real = r[None, :] < counts[:, None]
-    dst = torch.where(real, pos[:, None].long() + r[None, :], bs).clamp_(max=bs)
-    store.index_put_((torch.arange(B, device=qkv.device)[:, None].expand(B, Tn), dst), new_rows)
-    k_rows = buf[..., :nq].unflatten(-1, (H, N, hs))
-    v_rows = buf[..., nq:].unflatten(-1, (H, dv))
-    if one_row:
-        out = ops.diff_attention_decode_ragged(q[:, 0], k_rows, v_rows, coef, pos + counts).view(B, 1, H * dv)
-    elif ops.extend_supported(qkv.dtype, hs, N, dv):
-        out = ops.diff_attention_extend_ragged(q, k_rows, v_rows, coef, pos, counts)
-    else:
-        # no extend plan for this head size (as _extend_rows): one ragged decode per row,
-        # a padding row at length 0 (zeros)
-        zero = torch.zeros_like(pos)
-        out = torch.stack([ops.diff_attention_decode_ragged(q[:, i], k_rows, v_rows, coef,
-                                                            torch.where(counts > i, pos + (i + 1), zero))
-                           for i in range(Tn)], dim=1)
-    if hasattr(attn, "group_norm"):
-        gn = attn.group_norm
-        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
-    return attn.dropout(attn.proj(out))
+    B, Tn, _ = qkv.shape
+    q, k_new, _ = ops.split_packed(qkv, H, N, hs, dv)
+    k_rot = None
+    if pos is None:
+        out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
+        if freqs is not None:
+            k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
+            ops.rope_rows(k_new, k_rot, freqs[:Tn])
+    elif freqs is not None:
+        q, k_rot = _rope_rows_at(q, k_new, freqs, rows)
+    kv = cache.write_rows(layer, qkv, k_rot, (H, N, hs, dv), bs, tbl, pos, counts)
+    if pos is None:
+        pass
+    elif one_row:
+        out = cache.decode_rows(kv, q[:, 0], coef, tbl, pos + counts).view(B, 1, H * dv)
+    elif cache.kv_dtype is None and ops.extend_supported(qkv.dtype, hs, N, dv):
+        out = cache.extend_rows(kv, q, coef, tbl, pos, counts)
+    else:       # no extend plan for this head size, and no fp8 extend kernel
+        out = _decode_per_row(lambda i, n: cache.decode_rows(kv, q[:, i], coef, tbl, n), Tn, pos, counts)
+    return _attention_tail(attn, out)
 
 
-def _ragged_model_step(model, idx, cache: RaggedKVCache, pos, counts, gather=None, one_row: bool = False):
-    """The model's forward over (B, T) tokens, sequence b's at positions pos[b] ..
-    (``pos=None``: a right-padded prefill from position 0 through the fused training
-    forward).  Returns every row's logits (B, T, vocab), or with ``gather`` (long (B,))
-    row gather[b] of each sequence (B, vocab)."""
+def _seq_model_step(model, idx, cache, tbl, pos, counts, gather=None, one_row: bool = False):
+    """The model's forward over (B, T) tokens, sequence b's at positions pos[b] .., on a
+    ``RaggedKVCache`` (``tbl=None``) or a ``PagedKVCache``.  ``pos=None``: a right-padded
+    prefill from position 0 through the fused training forward.  Returns every row's logits
+    (B, T, vocab), or with ``gather`` (long (B,)) row gather[b] of each sequence (B, vocab)."""
     B, T = idx.shape
     r = torch.arange(T, device=idx.device)
     rows = r if pos is None else (pos[:, None].long() + r[None, :]).clamp_(max=model.block_size - 1)
@@ -476,15 +508,106 @@ def _ragged_model_step(model, idx, cache: RaggedKVCache, pos, counts, gather=Non
         x = x + model.position_embedding_table(rows)
     for layer, block in enumerate(model.blocks, 1):
         h = block.ln1(x)
-        if pos is None:
+        if pos is None and tbl is None:       # the ragged prefill is the one-length prefill
             x = x + _attention_step(block, h, layer, cache, 0)
         else:
-            x = x + _ragged_attention_step(block, h, layer, cache, pos, counts, rows, one_row)
+            x = x + _seq_attention_step(block, h, layer, cache, tbl, pos, counts, rows, one_row)
         x = x + block.ffwd(block.ln2(x))
     if gather is None:
         return model.lm_head(model.ln_f(x))
     x = x[torch.arange(B, device=idx.device), gather].unsqueeze(1)
     return model.lm_head(model.ln_f(x))[:, 0]
+
+
+# the names the ragged and the paged functions reach the step by (the CPU bookkeeping tests stub each)
+def _ragged_model_step(model, idx, cache: RaggedKVCache, pos, counts, gather=None, one_row: bool = False):
+    return _seq_model_step(model, idx, cache, None, pos, counts, gather, one_row)
+
+
+_paged_model_step = _seq_model_step
+
+
+def _check_prompts(prompts, bs: int) -> List[int]:
+    """The lengths of a prefill's prompts (one-dimensional LongTensors of 1 .. block_size tokens)."""
+    lens = []
+    for p in prompts:
+        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.long:
+            raise ValueError("prompts must be one-dimensional LongTensors")
+        if not 1 <= p.shape[0] <= bs:
+            raise ValueError(f"a prompt of {p.shape[0]} tokens is outside 1 .. block_size {bs}")
+        lens.append(p.shape[0])
+    if not lens:
+        raise ValueError("no prompts")
+    return lens
+
+
+def _check_counts(counts, names, have: Sequence[int], Tn: int, bs: int) -> List[int]:
+    """An append's ``counts`` as host integers (a tensor: one sync), each within 0 .. Tn and
+    within the window of its sequence (``names[b]`` at length ``have[b]``)."""
+    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+    if len(cnt) != len(have):
+        raise ValueError(f"{len(cnt)} counts for a batch of {len(have)}")
+    for name, c, n in zip(names, cnt, have):
+        if not 0 <= c <= Tn:
+            raise ValueError(f"sequence {name}: count {c} outside 0 .. {Tn}")
+        if n + c > bs:
+            raise ValueError(f"sequence {name}: appending {c} tokens at length {n} crosses block_size {bs}")
+    return cnt
+
+
+def _append_parts(step, lens, have: Sequence[int], cnt: Sequence[int], new_idx, bs: int, all_rows: bool):
+    """An append as one step, or as several narrower ones where a sequence sits so close to
+    block_size that its padded rows would not fit.  ``step(idx, pos, counts, gather)`` is the
+    cache's model step, ``lens`` / ``have`` the device and host lengths before the append.
+    Returns (the logits ``append_ragged`` documents, ``cnt`` on the device)."""
+    Tn = new_idx.shape[1]
+    cnt_dev = torch.tensor(cnt, dtype=torch.int32, device=new_idx.device)
+    out = None
+    done = 0
+    while done < Tn:
+        # the kernel needs pos[b] + width <= block_size of every sequence that still has real rows
+        live = [n + done for c, n in zip(cnt, have) if c > done]
+        w = min(Tn - done, bs - max(live)) if live else min(Tn - done, bs)
+        pos = lens + cnt_dev.clamp(max=done)
+        part_cnt = (cnt_dev - done).clamp_(0, w)
+        part_idx = new_idx[:, done:done + w]
+        if all_rows:
+            part = step(part_idx, pos, part_cnt, None)
+            out = part if out is None else torch.cat([out, part], dim=1)
+        else:
+            last = (cnt_dev.long() - 1 - done).clamp_(0, w - 1)
+            part = step(part_idx, pos, part_cnt, last)
+            here = ((cnt_dev > done) | (done == 0))[:, None]
+            out = part if out is None else torch.where(here, part, out)
+        done += w
+    return out, cnt_dev
+
+
+def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode):
+    """The reference's sampling loop (softmax of the last logits, one ``torch.multinomial``
+    over the whole batch) for ``max_new_tokens >= 1`` tokens; ``decode(tok, active)`` is the
+    cache's one-token step, ``active`` the device mask of the sequences that have not
+    sampled ``eos_id`` (None without one).  Returns (toks (B, max_new_tokens), keep): sequence
+    b keeps its first keep[b] tokens, up to its first ``eos_id`` -- the loop's one host sync."""
+    B = logits.shape[0]
+    active = None if eos_id is None else torch.ones(B, dtype=torch.bool, device=logits.device)
+    new = []
+    for step in range(max_new_tokens):
+        probs = F.softmax(logits, dim=-1)
+        tok = torch.multinomial(probs, num_samples=1)
+        new.append(tok)
+        if step + 1 == max_new_tokens:
+            break
+        if active is not None:
+            active = active & (tok[:, 0] != eos_id)
+        logits = decode(tok, active)
+    toks = torch.cat(new, dim=1)
+    keep = [max_new_tokens] * B
+    if eos_id is not None:
+        hit = toks == eos_id
+        first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
+        keep = first.tolist()
+    return toks, keep
 
 
 def _check_ragged(cache, B: int) -> None:
@@ -501,16 +624,7 @@ def prefill_ragged(model, prompts: Sequence[torch.Tensor], cache: RaggedKVCache)
     right-padded to the longest (the forward is causal, so the padding cannot reach a
     real row), every row's K_i / V is cached and ``lengths[b] = len(prompts[b])`` hides
     the padding.  Returns (B, vocab): each sequence's logits at its own last token."""
-    bs = model.block_size
-    lens = []
-    for p in prompts:
-        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.long:
-            raise ValueError("prompts must be one-dimensional LongTensors")
-        if not 1 <= p.shape[0] <= bs:
-            raise ValueError(f"a prompt of {p.shape[0]} tokens is outside 1 .. block_size {bs}")
-        lens.append(p.shape[0])
-    if not lens:
-        raise ValueError("no prompts")
+    lens = _check_prompts(prompts, model.block_size)
     if not isinstance(cache, RaggedKVCache):
         raise ValueError("prefill_ragged needs a RaggedKVCache")
     idx = torch.nn.utils.rnn.pad_sequence(list(prompts), batch_first=True)
@@ -572,34 +686,9 @@ def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, al
     _check_ragged(cache, B)
     if not cache.host_exact:
         cache.sync()
-    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
-    if len(cnt) != B:
-        raise ValueError(f"{len(cnt)} counts for a batch of {B}")
-    for b, (c, n) in enumerate(zip(cnt, cache.host_lengths)):
-        if not 0 <= c <= Tn:
-            raise ValueError(f"sequence {b}: count {c} outside 0 .. {Tn}")
-        if n + c > bs:
-            raise ValueError(f"sequence {b}: appending {c} tokens at length {n} crosses block_size {bs}")
-    dev = new_idx.device
-    cnt_dev = torch.tensor(cnt, dtype=torch.int32, device=dev)
-    out = None
-    done = 0
-    while done < Tn:
-        # the kernel needs pos[b] + width <= block_size of every sequence that still has real rows
-        live = [n + done for c, n in zip(cnt, cache.host_lengths) if c > done]
-        w = min(Tn - done, bs - max(live)) if live else min(Tn - done, bs)
-        pos = cache.lengths + cnt_dev.clamp(max=done)
-        part_cnt = (cnt_dev - done).clamp_(0, w)
-        part_idx = new_idx[:, done:done + w]
-        if all_rows:
-            part = _ragged_model_step(model, part_idx, cache, pos, part_cnt)
-            out = part if out is None else torch.cat([out, part], dim=1)
-        else:
-            last = (cnt_dev.long() - 1 - done).clamp_(0, w - 1)
-            part = _ragged_model_step(model, part_idx, cache, pos, part_cnt, gather=last)
-            here = ((cnt_dev > done) | (done == 0))[:, None]
-            out = part if out is None else torch.where(here, part, out)
-        done += w
+    cnt = _check_counts(counts, range(B), cache.host_lengths, Tn, bs)
+    out, cnt_dev = _append_parts(lambda idx, pos, c, last: _ragged_model_step(model, idx, cache, pos, c, last),
+                                 cache.lengths, cache.host_lengths, cnt, new_idx, bs, all_rows)
     cache.lengths = cache.lengths + cnt_dev
     cache.host_lengths = [n + c for n, c in zip(cache.host_lengths, cnt)]
     return out
@@ -629,23 +718,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     logits = prefill_ragged(model, prompts, cache)
     if max_new_tokens < 1:
         return [p.clone() for p in prompts]
-    active = None if eos_id is None else torch.ones(len(prompts), dtype=torch.bool, device=logits.device)
-    new = []
-    for step in range(max_new_tokens):
-        probs = F.softmax(logits, dim=-1)
-        tok = torch.multinomial(probs, num_samples=1)
-        new.append(tok)
-        if step + 1 == max_new_tokens:
-            break
-        if active is not None:
-            active = active & (tok[:, 0] != eos_id)
-        logits = decode_ragged(model, tok, cache, active)
-    toks = torch.cat(new, dim=1)
-    keep = [max_new_tokens] * len(prompts)
-    if eos_id is not None:
-        hit = toks == eos_id
-        first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
-        keep = first.tolist()
+    toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
+                                lambda tok, active: decode_ragged(model, tok, cache, active))
     return [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(prompts)]
 
 
@@ -731,6 +805,41 @@ class PagedKVCache(KVCache):
             sc = torch.empty(sshape, device=device, dtype=torch.float32)
             self.pool[layer], self.scale_pool[layer] = buf, sc
         return buf, sc
+
+    def write_rows(self, layer: int, qkv, k_rot, dims, bs: int, tbl, pos, counts):
+        """Scatter a step's new rows: the real ones to row (pos[b] + r) % P of page
+        tbl[b, (pos[b] + r) // P] (``pos=None``: the prefill's, from row 0), the padding to
+        the spare page -- one ``index_put_``, or on an fp8 pool one ``ops.kv_quant_rows``
+        (straight from the RoPE temporary and the V slice of ``qkv``: no concatenated copy).
+        Returns the pool views the kernels read: (k_pool, v_pool), fp8 (k, v, scales)."""
+        H, N, hs, dv = dims
+        B, Tn, W = qkv.shape
+        nq = H * N * hs
+        P, npg = self.page_size, self.num_pages
+        r = torch.arange(Tn, device=qkv.device)
+        at = r[None, :].expand(B, Tn) if pos is None else pos[:, None].long() + r[None, :]
+        real = (r[None, :] < counts[:, None]) & (at < bs)
+        page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
+        if self.kv_dtype is None:
+            pool = self.layer_pool(layer, W - nq, qkv)
+            pool.index_put_((page, at % P), _packed_new_rows(qkv, k_rot, nq))
+            return pool[:npg, :, :nq].unflatten(-1, (H, N, hs)), pool[:npg, :, nq:].unflatten(-1, (H, dv))
+        pool, scales = self.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
+        k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
+        v_all = pool[..., nq:].unflatten(-1, (H, dv))
+        s_all = scales.unflatten(-1, (H, N + 1))
+        _, k_new, v_new = ops.split_packed(qkv, H, N, hs, dv)
+        ops.kv_quant_rows(k_new if k_rot is None else k_rot, v_new, k_all, v_all, s_all,
+                          (page * P + at % P).to(torch.int32).flatten())
+        return k_all[:npg], v_all[:npg], s_all[:npg]
+
+    def decode_rows(self, kv, q, coef, tbl, lengths):
+        if self.kv_dtype is None:
+            return ops.diff_attention_decode_paged(q, *kv, coef, tbl, lengths)
+        return ops.diff_attention_decode_paged_fp8(q, *kv, coef, tbl, lengths)
+
+    def extend_rows(self, kv, q, coef, tbl, pos, counts):
+        return ops.diff_attention_extend_paged(q, *kv, coef, tbl, pos, counts)
 
     def cache_bytes(self) -> int:
         """Bytes the pools of every layer hold (spare pages included)."""
@@ -895,143 +1004,6 @@ class PagedKVCache(KVCache):
         return self._new_seq(list(self.pages[seq]), self.host_lengths[seq])
 
 
-def _paged_attention_step(block, x, layer: int, cache: PagedKVCache, tbl, pos, counts, rows, one_row: bool):
-    """``_ragged_attention_step`` over the page pool: ``tbl`` is the step's contiguous
-    (B, max_pages) table.  The real rows' K_i / V are scattered to row (pos[b] + r) % P of
-    page tbl[b, (pos[b] + r) // P], the padding rows' to the spare page, by one
-    ``index_put_``.  ``pos=None``: the right-padded prefill from position 0 (fused
-    training forward; counts = the prompt lengths)."""
-    attn, H, N, hs, dv, bs = _spec(block)
-    consts = cache.consts.get(layer)
-    if consts is None:
-        consts = _constants(attn, layer, H, hs, bs, x.device)
-        cache.consts[layer] = consts
-    weight, coef, freqs = consts
-    if cache.kv_dtype is not None:
-        return _paged_attention_step_fp8(attn, x, layer, cache, tbl, pos, counts, rows, one_row,
-                                         (H, N, hs, dv, bs), weight, coef, freqs)
-    qkv = F.linear(x, weight)
-    B, Tn, W = qkv.shape
-    nq = H * N * hs
-    P, npg = cache.page_size, cache.num_pages
-    pool = cache.layer_pool(layer, W - nq, qkv)
-    r = torch.arange(Tn, device=qkv.device)
-    new_rows = qkv[..., nq:]
-    if pos is None:
-        out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
-        if freqs is not None:
-            k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
-            ops.rope_rows(qkv[..., nq:2 * nq].unflatten(-1, (H, N, hs)), k_rot, freqs[:Tn])
-            new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
-        at = r[None, :].expand(B, Tn)
-    else:
-        q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
-        if freqs is not None:
-            tab = freqs[rows.flatten()]
-            k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
-            q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
-            k_rot = torch.empty_like(q_rot)
-            ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
-            ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
-            q = q_rot
-            new_rows = torch.cat([k_rot.flatten(2), qkv[..., 2 * nq:]], dim=-1)
-        at = pos[:, None].long() + r[None, :]
-    real = (r[None, :] < counts[:, None]) & (at < bs)
-    page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
-    pool.index_put_((page, at % P), new_rows)
-    if pos is not None:
-        k_pool = pool[:npg, :, :nq].unflatten(-1, (H, N, hs))
-        v_pool = pool[:npg, :, nq:].unflatten(-1, (H, dv))
-        if one_row:
-            out = ops.diff_attention_decode_paged(q[:, 0], k_pool, v_pool, coef, tbl, pos + counts).view(B, 1, H * dv)
-        elif ops.extend_supported(qkv.dtype, hs, N, dv):
-            out = ops.diff_attention_extend_paged(q, k_pool, v_pool, coef, tbl, pos, counts)
-        else:
-            # no extend plan for this head size: one paged decode per row, a padding row at length 0
-            zero = torch.zeros_like(pos)
-            out = torch.stack([ops.diff_attention_decode_paged(q[:, i], k_pool, v_pool, coef, tbl,
-                                                               torch.where(counts > i, pos + (i + 1), zero))
-                               for i in range(Tn)], dim=1)
-    if hasattr(attn, "group_norm"):
-        gn = attn.group_norm
-        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
-    return attn.dropout(attn.proj(out))
-
-
-def _paged_attention_step_fp8(attn, x, layer: int, cache: PagedKVCache, tbl, pos, counts, rows, one_row: bool,
-                              spec, weight, coef, freqs):
-    """``_paged_attention_step`` on an fp8 pool (``kv_dtype="fp8_e4m3"``).  The prefill's
-    attention runs the fused training forward on the unquantised activations; every step
-    writes its new rows through ``ops.kv_quant_rows`` (straight from the RoPE temporary and
-    the V slice of ``qkv``: no concatenated copy); a one-row step runs
-    ``ops.diff_attention_decode_paged_fp8``, a multi-row step one such decode per row (there
-    is no fp8 extend kernel)."""
-    H, N, hs, dv, bs = spec
-    qkv = F.linear(x, weight)
-    B, Tn, W = qkv.shape
-    nq = H * N * hs
-    P, npg = cache.page_size, cache.num_pages
-    pool, scales = cache.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
-    r = torch.arange(Tn, device=qkv.device)
-    q = qkv[:, :, :nq].unflatten(-1, (H, N, hs))
-    k_new = qkv[:, :, nq:2 * nq].unflatten(-1, (H, N, hs))
-    v_new = qkv[..., 2 * nq:].unflatten(-1, (H, dv))
-    if pos is None:
-        out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
-        if freqs is not None:
-            k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
-            ops.rope_rows(k_new, k_rot, freqs[:Tn])
-            k_new = k_rot
-        at = r[None, :].expand(B, Tn)
-    else:
-        if freqs is not None:
-            tab = freqs[rows.flatten()]
-            q_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
-            k_rot = torch.empty_like(q_rot)
-            ops.rope_rows(q.reshape(1, B * Tn, H, N, hs), q_rot.view(1, B * Tn, H, N, hs), tab)
-            ops.rope_rows(k_new.reshape(1, B * Tn, H, N, hs), k_rot.view(1, B * Tn, H, N, hs), tab)
-            q, k_new = q_rot, k_rot
-        at = pos[:, None].long() + r[None, :]
-    real = (r[None, :] < counts[:, None]) & (at < bs)
-    page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
-    slots = (page * P + at % P).to(torch.int32).flatten()
-    k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
-    v_all = pool[..., nq:].unflatten(-1, (H, dv))
-    s_all = scales.unflatten(-1, (H, N + 1))
-    ops.kv_quant_rows(k_new, v_new, k_all, v_all, s_all, slots)
-    if pos is not None:
-        k_pool, v_pool, s_pool = k_all[:npg], v_all[:npg], s_all[:npg]
-        if one_row:
-            out = ops.diff_attention_decode_paged_fp8(q[:, 0], k_pool, v_pool, s_pool, coef, tbl,
-                                                      pos + counts).view(B, 1, H * dv)
-        else:
-            zero = torch.zeros_like(pos)
-            out = torch.stack([ops.diff_attention_decode_paged_fp8(q[:, i], k_pool, v_pool, s_pool, coef, tbl,
-                                                                   torch.where(counts > i, pos + (i + 1), zero))
-                               for i in range(Tn)], dim=1)
-    if hasattr(attn, "group_norm"):
-        gn = attn.group_norm
-        out = ops.group_ln_scale(out, gn.weight, gn.bias, gn.eps, mha_out_scale(attn.lambda_init))
-    return attn.dropout(attn.proj(out))
-
-
-def _paged_model_step(model, idx, cache: PagedKVCache, tbl, pos, counts, gather=None, one_row: bool = False):
-    """``_ragged_model_step`` over the page pool (``pos=None``: the prefill)."""
-    B, T = idx.shape
-    r = torch.arange(T, device=idx.device)
-    rows = r if pos is None else (pos[:, None].long() + r[None, :]).clamp_(max=model.block_size - 1)
-    x = model.token_embedding_table(idx)
-    if hasattr(model, "position_embedding_table"):
-        x = x + model.position_embedding_table(rows)
-    for layer, block in enumerate(model.blocks, 1):
-        x = x + _paged_attention_step(block, block.ln1(x), layer, cache, tbl, pos, counts, rows, one_row)
-        x = x + block.ffwd(block.ln2(x))
-    if gather is None:
-        return model.lm_head(model.ln_f(x))
-    x = x[torch.arange(B, device=idx.device), gather].unsqueeze(1)
-    return model.lm_head(model.ln_f(x))[:, 0]
-
-
 def _paged_gather(cache: PagedKVCache, seqs: Sequence[int]):
     """The step's view of the device state: (slots, contiguous (B, max_pages) table, (B,) lengths)."""
     cache._flush()
@@ -1048,15 +1020,7 @@ def prefill_paged(model, prompts: Sequence[torch.Tensor], cache: PagedKVCache):
     pool does not hold them), and each layer scatters its K_i / V rows
     into them.  Returns (sequence ids, (B, vocab) logits at each prompt's last token)."""
     bs = model.block_size
-    lens = []
-    for p in prompts:
-        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.long:
-            raise ValueError("prompts must be one-dimensional LongTensors")
-        if not 1 <= p.shape[0] <= bs:
-            raise ValueError(f"a prompt of {p.shape[0]} tokens is outside 1 .. block_size {bs}")
-        lens.append(p.shape[0])
-    if not lens:
-        raise ValueError("no prompts")
+    lens = _check_prompts(prompts, bs)
     if not isinstance(cache, PagedKVCache):
         raise ValueError("prefill_paged needs a PagedKVCache")
     need = sum(cache._need(n) for n in lens)
@@ -1136,38 +1100,13 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
     if len(seqs) != B:
         raise ValueError(f"batch size {B} differs from the {len(seqs)} sequences named")
     cache.sync()
-    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
-    if len(cnt) != B:
-        raise ValueError(f"{len(cnt)} counts for a batch of {B}")
     have = [cache.host_lengths[q] for q in seqs]
-    for b, (c, n) in enumerate(zip(cnt, have)):
-        if not 0 <= c <= Tn:
-            raise ValueError(f"sequence {seqs[b]}: count {c} outside 0 .. {Tn}")
-        if n + c > bs:
-            raise ValueError(f"sequence {seqs[b]}: appending {c} tokens at length {n} crosses block_size {bs}")
+    cnt = _check_counts(counts, seqs, have, Tn, bs)
     writers = [b for b in range(B) if cnt[b] > 0]
     cache._prepare_writes([seqs[b] for b in writers], [have[b] + cnt[b] for b in writers])
     sl, tbl, lens = _paged_gather(cache, seqs)
-    dev = new_idx.device
-    cnt_dev = torch.tensor(cnt, dtype=torch.int32, device=dev)
-    out = None
-    done = 0
-    while done < Tn:
-        # the kernel needs pos[b] + width <= block_size of every sequence that still has real rows
-        live = [n + done for c, n in zip(cnt, have) if c > done]
-        w = min(Tn - done, bs - max(live)) if live else min(Tn - done, bs)
-        pos = lens + cnt_dev.clamp(max=done)
-        part_cnt = (cnt_dev - done).clamp_(0, w)
-        part_idx = new_idx[:, done:done + w]
-        if all_rows:
-            part = _paged_model_step(model, part_idx, cache, tbl, pos, part_cnt)
-            out = part if out is None else torch.cat([out, part], dim=1)
-        else:
-            last = (cnt_dev.long() - 1 - done).clamp_(0, w - 1)
-            part = _paged_model_step(model, part_idx, cache, tbl, pos, part_cnt, gather=last)
-            here = ((cnt_dev > done) | (done == 0))[:, None]
-            out = part if out is None else torch.where(here, part, out)
-        done += w
+    out, cnt_dev = _append_parts(lambda idx, pos, c, last: _paged_model_step(model, idx, cache, tbl, pos, c, last),
+                                 lens, have, cnt, new_idx, bs, all_rows)
     cache.lengths.index_copy_(0, sl, lens + cnt_dev)
     for q, n, c in zip(seqs, have, cnt):
         cache.host_lengths[q] = cache.host_low[q] = n + c
@@ -1209,23 +1148,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     if max_new_tokens >= 1:
         if n_samples > 1:
             logits = logits.repeat_interleave(n_samples, dim=0)
-        active = None if eos_id is None else torch.ones(len(seqs), dtype=torch.bool, device=logits.device)
-        new = []
-        for step in range(max_new_tokens):
-            probs = F.softmax(logits, dim=-1)
-            tok = torch.multinomial(probs, num_samples=1)
-            new.append(tok)
-            if step + 1 == max_new_tokens:
-                break
-            if active is not None:
-                active = active & (tok[:, 0] != eos_id)
-            logits = decode_paged(model, seqs, tok, cache, active)
-        toks = torch.cat(new, dim=1)
-        keep = [max_new_tokens] * len(seqs)
-        if eos_id is not None:
-            hit = toks == eos_id
-            first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, max_new_tokens)
-            keep = first.tolist()
+        toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
+                                    lambda tok, active: decode_paged(model, seqs, tok, cache, active))
         outs = [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(outs)]
     else:
         outs = [p.clone() for p in outs]

@@ -686,6 +686,39 @@ def rope_rows(src: Tensor, dst: Tensor, table: Tensor) -> None:
     _lib.check(lib.dta_rope(ra, _lib.stream_handle(src.device)))
 
 
+def _decode(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, bound: int, T_cap: int,
+            length_dev: Optional[Tensor] = None, lengths: Optional[Tensor] = None, page=None,
+            scale_pool: Optional[Tensor] = None) -> Tensor:
+    """The launch every decode op ends in, on views its caller has checked.  ``bound``: the host
+    length (upper bound), which sizes the grid.  ``lengths`` None: ``dta_attn_decode`` with its
+    optional device scalar ``length_dev``; else the ragged entry point, with ``page`` =
+    (block_table, P, max_pages, n_pages) the paged one and with ``scale_pool`` the fp8 one."""
+    B, H, N, hs = q.shape
+    dv = v.shape[-1]
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
+    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    head = (_lib.dtype_code(q.dtype), B, H, N, hs, dv, bound, T_cap, 1.0 / math.sqrt(hs),
+            _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k), _lib.tensor5(v), _lib.tensor5(o),
+            coef.data_ptr(), ws.data_ptr())
+    stream = _lib.stream_handle(q.device)
+    if lengths is None:
+        rc = lib.dta_attn_decode(_lib.DecodeArgs(*head, _lib.ptr(length_dev)), stream)
+    elif page is None:
+        rc = lib.dta_attn_decode_ragged(_lib.DecodeRaggedArgs(*head, lengths.data_ptr()), stream)
+    else:
+        table, P, max_pages, n_pages = page
+        tail = (lengths.data_ptr(), P, max_pages, n_pages, table.data_ptr())
+        if scale_pool is None:
+            rc = lib.dta_attn_decode_paged(_lib.DecodePagedArgs(*head, *tail), stream)
+        else:
+            rc = lib.dta_attn_decode_paged_fp8(
+                _lib.DecodePagedFp8Args(*head, *tail, scale_pool.data_ptr(), scale_pool.stride(0)), stream)
+    _lib.check(rc)
+    return o.view(B, H * dv)
+
+
 def diff_attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, length: int,
                           length_dev: Optional[Tensor] = None) -> Tensor:
     """One new query row per (b, h) against the first ``length`` cached keys:
@@ -713,16 +746,7 @@ def diff_attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
         _require_gpu(length_dev)
         if length_dev.dtype != torch.int32 or length_dev.numel() != 1:
             raise RuntimeError("length_dev must be one device int32")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
-    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    a = _lib.DecodeArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, length, T_cap, 1.0 / math.sqrt(hs),
-                        _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_cache), _lib.tensor5(v_cache),
-                        _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(),
-                        None if length_dev is None else length_dev.data_ptr())
-    _lib.check(lib.dta_attn_decode(a, _lib.stream_handle(q.device)))
-    return o.view(B, H * dv)
+    return _decode(lib, q, k_cache, v_cache, coef, length, T_cap, length_dev=length_dev)
 
 
 # ------------------------------------------------------------------ extend ---
@@ -730,6 +754,37 @@ def extend_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
     """Whether ``diff_attention_extend`` has a kernel plan for this shape
     (dta_extend_supported): hs % 16 == 0 in 16..128, dv % 32 == 0 up to 256, N <= 8."""
     return bool(_lib.load().dta_extend_supported(_lib.dtype_code(dtype), hs, N, dv))
+
+
+def _extend(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos: Optional[int] = None,
+            pos_dev: Optional[Tensor] = None, counts: Optional[Tensor] = None, page=None) -> Tensor:
+    """The tail every extend op ends in, on views its caller has checked: the kernel-plan check
+    (no fallback), then the launch.  ``pos``: the host position of ``dta_attn_extend``;
+    ``pos_dev`` / ``counts``: the ragged entry point's, with ``page`` = (block_table, P,
+    max_pages, n_pages) the paged one's."""
+    B, Tq, H, N, hs = q.shape
+    dv = v.shape[-1]
+    if not extend_supported(q.dtype, hs, N, dv):
+        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
+    if B * Tq == 0:
+        return o.view(B, Tq, H * dv)
+    head = (_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq)
+    mid = (T_cap, 1.0 / math.sqrt(hs), _lib.tensor5(q), _lib.tensor5(k), _lib.tensor5(v), _lib.tensor5(o),
+           coef.data_ptr())
+    stream = _lib.stream_handle(q.device)
+    if pos_dev is None:
+        rc = lib.dta_attn_extend(_lib.ExtendArgs(*head, pos, *mid), stream)
+    elif page is None:
+        rc = lib.dta_attn_extend_ragged(_lib.ExtendRaggedArgs(*head, *mid, pos_dev.data_ptr(), _lib.ptr(counts)),
+                                        stream)
+    else:
+        table, P, max_pages, n_pages = page
+        rc = lib.dta_attn_extend_paged(_lib.ExtendPagedArgs(*head, *mid, pos_dev.data_ptr(), _lib.ptr(counts),
+                                                            P, max_pages, n_pages, table.data_ptr()), stream)
+    _lib.check(rc)
+    return o.view(B, Tq, H * dv)
 
 
 def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: int) -> Tensor:
@@ -758,17 +813,7 @@ def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
     pos = int(pos)
     if pos < 0 or pos + Tq > T_cap:
         raise RuntimeError(f"extend rows {pos}..{pos + Tq - 1} outside the cache's {T_cap} rows")
-    if not extend_supported(q.dtype, hs, N, dv):
-        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
-    if B * Tq == 0:
-        return o.view(B, Tq, H * dv)
-    a = _lib.ExtendArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, pos, T_cap, 1.0 / math.sqrt(hs),
-                        _lib.tensor5(q), _lib.tensor5(k_cache), _lib.tensor5(v_cache), _lib.tensor5(o),
-                        coef.data_ptr())
-    _lib.check(lib.dta_attn_extend(a, _lib.stream_handle(q.device)))
-    return o.view(B, Tq, H * dv)
+    return _extend(lib, q, k_cache, v_cache, coef, T_cap, pos=pos)
 
 
 # ------------------------------------------------------------------ ragged ---
@@ -802,15 +847,7 @@ def diff_attention_decode_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
     if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
         raise RuntimeError("q, k_cache and v_cache must share a dtype")
     _batch_int32(lengths, B, q, "lengths")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
-    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    a = _lib.DecodeRaggedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
-                              _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_cache), _lib.tensor5(v_cache),
-                              _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr())
-    _lib.check(lib.dta_attn_decode_ragged(a, _lib.stream_handle(q.device)))
-    return o.view(B, H * dv)
+    return _decode(lib, q, k_cache, v_cache, coef, max_length, T_cap, lengths=lengths)
 
 
 def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: Tensor,
@@ -844,21 +881,21 @@ def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
         _batch_int32(counts, B, q, "counts")
     if Tq > T_cap:
         raise RuntimeError(f"{Tq} new rows do not fit the cache's {T_cap} rows")
-    if not extend_supported(q.dtype, hs, N, dv):
-        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
-    if B * Tq == 0:
-        return o.view(B, Tq, H * dv)
-    a = _lib.ExtendRaggedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, T_cap, 1.0 / math.sqrt(hs),
-                              _lib.tensor5(q), _lib.tensor5(k_cache), _lib.tensor5(v_cache), _lib.tensor5(o),
-                              coef.data_ptr(), pos.data_ptr(), None if counts is None else counts.data_ptr())
-    _lib.check(lib.dta_attn_extend_ragged(a, _lib.stream_handle(q.device)))
-    return o.view(B, Tq, H * dv)
+    return _extend(lib, q, k_cache, v_cache, coef, T_cap, pos_dev=pos, counts=counts)
 
 
 # ------------------------------------------------------------------- paged ---
 PAGE_SIZES = (32, 64, 128, 256)
+
+
+def _table_pages(block_table: Tensor, B: int, q: Tensor) -> int:
+    """Checks of a step's block table; returns max_pages."""
+    if (not isinstance(block_table, Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != q.device):
+        raise RuntimeError(f"block_table must be a device int32 tensor of shape ({B}, max_pages) on {q.device}")
+    if not block_table.is_contiguous():
+        raise RuntimeError("block_table must be contiguous")
+    return block_table.shape[1]
 
 
 def _paged_views(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, B: int, H: int, N: int, hs: int):
@@ -874,12 +911,7 @@ def _paged_views(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor,
         raise RuntimeError("k_pool/v_pool shapes do not match q")
     if q.dtype != k_pool.dtype or q.dtype != v_pool.dtype:
         raise RuntimeError("q, k_pool and v_pool must share a dtype")
-    if (not isinstance(block_table, Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
-            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != q.device):
-        raise RuntimeError(f"block_table must be a device int32 tensor of shape ({B}, max_pages) on {q.device}")
-    if not block_table.is_contiguous():
-        raise RuntimeError("block_table must be contiguous")
-    return n_pages, P, block_table.shape[1], dv
+    return n_pages, P, _table_pages(block_table, B, q), dv
 
 
 def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
@@ -905,16 +937,8 @@ def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
     if not 1 <= max_length <= T_cap:
         raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
     _batch_int32(lengths, B, q, "lengths")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
-    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    a = _lib.DecodePagedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
-                             _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_pool), _lib.tensor5(v_pool),
-                             _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr(),
-                             P, max_pages, n_pages, block_table.data_ptr())
-    _lib.check(lib.dta_attn_decode_paged(a, _lib.stream_handle(q.device)))
-    return o.view(B, H * dv)
+    return _decode(lib, q, k_pool, v_pool, coef, max_length, T_cap, lengths=lengths,
+                   page=(block_table, P, max_pages, n_pages))
 
 
 def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
@@ -941,18 +965,8 @@ def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
         _batch_int32(counts, B, q, "counts")
     if Tq > T_cap:
         raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
-    if not extend_supported(q.dtype, hs, N, dv):
-        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
-    if B * Tq == 0:
-        return o.view(B, Tq, H * dv)
-    a = _lib.ExtendPagedArgs(_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, T_cap, 1.0 / math.sqrt(hs),
-                             _lib.tensor5(q), _lib.tensor5(k_pool), _lib.tensor5(v_pool), _lib.tensor5(o),
-                             coef.data_ptr(), pos.data_ptr(), None if counts is None else counts.data_ptr(),
-                             P, max_pages, n_pages, block_table.data_ptr())
-    _lib.check(lib.dta_attn_extend_paged(a, _lib.stream_handle(q.device)))
-    return o.view(B, Tq, H * dv)
+    return _extend(lib, q, k_pool, v_pool, coef, T_cap, pos_dev=pos, counts=counts,
+                   page=(block_table, P, max_pages, n_pages))
 
 
 # --------------------------------------------------------------- fp8 pages ---
@@ -1042,28 +1056,14 @@ def diff_attention_decode_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
     n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
     if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
         raise RuntimeError("the pool views do not match q")
-    if (not isinstance(block_table, Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
-            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != q.device):
-        raise RuntimeError(f"block_table must be a device int32 tensor of shape ({B}, max_pages) on {q.device}")
-    if not block_table.is_contiguous():
-        raise RuntimeError("block_table must be contiguous")
-    max_pages = block_table.shape[1]
+    max_pages = _table_pages(block_table, B, q)
     T_cap = max_pages * P
     max_length = T_cap if max_length is None else int(max_length)
     if not 1 <= max_length <= T_cap:
         raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
     _batch_int32(lengths, B, q, "lengths")
-    coef = coef.detach().to(torch.float32).contiguous()
-    o = torch.empty(B, 1, H, dv, device=q.device, dtype=q.dtype)
-    nbytes = lib.dta_attn_decode_workspace_bytes(B, H, N, hs, dv, T_cap)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    a = _lib.DecodePagedFp8Args(_lib.dtype_code(q.dtype), B, H, N, hs, dv, max_length, T_cap, 1.0 / math.sqrt(hs),
-                                _lib.tensor5(q.unsqueeze(1)), _lib.tensor5(k_pool_u8), _lib.tensor5(v_pool_u8),
-                                _lib.tensor5(o), coef.data_ptr(), ws.data_ptr(), lengths.data_ptr(),
-                                P, max_pages, n_pages, block_table.data_ptr(),
-                                scale_pool.data_ptr(), scale_pool.stride(0))
-    _lib.check(lib.dta_attn_decode_paged_fp8(a, _lib.stream_handle(q.device)))
-    return o.view(B, H * dv)
+    return _decode(lib, q, k_pool_u8, v_pool_u8, coef, max_length, T_cap, lengths=lengths,
+                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool)
 
 
 def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,

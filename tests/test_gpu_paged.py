@@ -363,6 +363,27 @@ def test_append_paged_fallback_head_size_40():
             assert rel_err(rows[i, :counts[i]], _full(model, seq)[-counts[i]:]) <= 1e-4, i
 
 
+def test_append_paged_fallback_equals_append_ragged_bitwise():
+    """The per-row fallback (hs = 40) of the paged multi-row step gives the ragged one's real rows, bit for bit."""
+    torch.manual_seed(4)
+    model = C.StandardTransformer(97, 160, 4, 2, 64, 0.0).to(DEV).eval()      # hs = dv = 40, N = 1, fp32
+    assert not ops.extend_supported(torch.float32, 40, 1, 40)
+    prompts = _prompts(13, [5, 17, 40])
+    new = torch.randint(0, 97, (3, 4), generator=torch.Generator().manual_seed(14)).to(DEV)
+    counts = [4, 0, 2]
+    ragged, paged = kv_cache.RaggedKVCache(), kv_cache.PagedKVCache(POOL, 32)
+    with torch.no_grad():
+        kv_cache.prefill_ragged(model, prompts, ragged)
+        ids, _ = kv_cache.prefill_paged(model, prompts, paged)
+        want = kv_cache.append_ragged(model, new, counts, ragged, all_rows=True)
+        got = kv_cache.append_paged(model, ids, new, counts, paged, all_rows=True)
+    assert got.shape == want.shape == (3, 4, 97)
+    for b, c in enumerate(counts):
+        assert torch.equal(got[b, :c], want[b, :c]), b
+    assert [paged.sync()[q] for q in ids] == ragged.sync() == [9, 17, 42]
+    assert paged.lengths[[paged.slot[q] for q in ids]].tolist() == ragged.lengths.tolist() == [9, 17, 42]
+
+
 @pytest.mark.parametrize("which", ["diff", "alt3", "ctrl"])
 def test_fork_shares_pages_and_copies_on_write(which):
     model = _model(which)
