@@ -252,6 +252,18 @@ __device__ __forceinline__ void lgkm_wait() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(N) : "memory");
 }
 
+// Depth of those pipelines: operand reads in flight ahead of the MFMA that consumes them
+// (the forward's 32-key-tile score chains; attn_dq's dP and score chains).  A counted wait
+// leaves at most that many reads outstanding, and lgkmcnt is a 4-bit counter.
+#ifndef DTA_FWD_PIPE
+#define DTA_FWD_PIPE 3
+#endif
+#ifndef DTA_DQ_PIPE
+#define DTA_DQ_PIPE 3
+#endif
+static_assert(DTA_FWD_PIPE >= 1 && DTA_FWD_PIPE <= 15, "DTA_FWD_PIPE: 1 .. 15 reads ahead");
+static_assert(DTA_DQ_PIPE >= 1 && DTA_DQ_PIPE <= 15, "DTA_DQ_PIPE: 1 .. 15 reads ahead");
+
 // One score chain S[kb] += K[kb] Q^T over NSQ k-steps (32-row key blocks kb < NKB, K rows as
 // the A operand) with every operand read D reads ahead of its MFMA.  Per k-step s: the Q
 // fragment (QL: from LDS at bQ ^ 32 s + QOFF, else qreg[s]) then the NKB K fragments
@@ -629,39 +641,6 @@ inline bool kv_layout_ok(const P& p, int es) {
 //   dP'  = dO V^T - delta_0
 // P_i = exp2(S'_i) with no fma; dS_0 / c_0 = P_0 dP', dS_i / c_i = P_i (dP' + delta_0 -
 // delta_i); c_i and the softmax scale are applied once in the dQ epilogue.
-#ifndef DTA_FWD_IGLP
-#define DTA_FWD_IGLP -1          // A/B: __builtin_amdgcn_iglp_opt(k) in the tile loop (-1 = off); k = 0: no effect on any kernel (r06u), 1: compiler out of memory
-#endif
-#ifndef DTA_DQ_IGLP
-#define DTA_DQ_IGLP -1
-#endif
-#ifndef DTA_DKDV_IGLP
-#define DTA_DKDV_IGLP -1
-#endif
-#ifndef DTA_DQ_SEED
-#define DTA_DQ_SEED 1
-#endif
-#ifndef DTA_DQ_PIPE
-#define DTA_DQ_PIPE 3
-#endif
-#ifndef DTA_FWD_PIPE
-#define DTA_FWD_PIPE 3
-#endif
-#ifndef DTA_FWD_TR_EARLY
-#define DTA_FWD_TR_EARLY 0       // A/B: the forward's first d-block V^T reads issued before the last softmax
-#endif
-#ifndef DTA_FWD_SEED
-#define DTA_FWD_SEED 0           // A/B: forward Q_i pre-scaled by scale*log2e, S seeded with -m by one MFMA (FAST tiles): r06e cfg2 fwd 0.874 -> 0.854 ms, but the bf16 Q*scale rounding moved the forward LSE / O_i off the backward kernels and broke the d(coef) / large-logit bars (r06f): off
-#endif
-#ifndef DTA_FWD_PK
-#define DTA_FWD_PK 0             // A/B: the forward's exp arguments and row sums as packed fp32 pairs (v_pk_*): 161 -> 102 VALU issues, fwd +0.3..0.7% (r06p2): off
-#endif
-#ifndef DTA_FWD_FAST
-#define DTA_FWD_FAST 1
-#endif
-#ifndef DTA_DKDV_FUSE1
-#define DTA_DKDV_FUSE1 1
-#endif
 template <class E>
 __device__ __forceinline__ typename Ops<E>::frag seed_frag(float v, int hf) {
   typename Ops<E>::frag f = Ops<E>::zero();
@@ -696,17 +675,11 @@ struct FwdChunk {
   static constexpr int DVC = DV <= cap ? DV : (cap >= 128 && DV % 128 == 0 ? 128 : (cap >= 64 ? 64 : 32));
 };
 
-#ifndef DTA_EPI_SKIP
-#define DTA_EPI_SKIP 0           // measurement only (wrong results): 1 skips the attention kernels' output stores, 2 the forward's O_i stores
-#endif
-#ifndef DTA_FWD_BN32
-#define DTA_FWD_BN32 0           // A/B: the paired forward plans with 32-key tiles
-#endif
 template <class E, int HS, int N, int DVC, int NW, bool QREG, int QRH = 0>
 struct FwdCfg {
   // QRH > 0 (paired plan): the first QRH branches' Q rows stay in registers
   static constexpr bool PAIR = NW == 4 && !QREG && sizeof(E) == 2 && N * DVC / 2 <= 128;
-  static constexpr int BN = (PAIR && (QRH == 0 || DTA_FWD_BN32)) ? 32 : FwdTile<E>::BN;
+  static constexpr int BN = (PAIR && QRH == 0) ? 32 : FwdTile<E>::BN;
   static constexpr int BM = NW * 32;
   static constexpr int HSP = img_cols(HS), DVP = img_cols(DVC);     // LDS image widths
   static constexpr int nQ = QREG ? 0 : (N - QRH) * BM * HSP;
@@ -728,10 +701,7 @@ struct FwdCfg {
 // (profiles/r05c_ab_pair_n1.json, outputs bitwise equal): cfg3 N = 3 forward 0.398 ->
 // 0.369 ms, N = 4 0.506 -> 0.484; control hs 64 forward 0.222 -> 0.199, dQ 0.273 -> 0.252;
 // control hs 128 (cfg5) dQ 11.36 -> 10.73 ms but forward 8.60 -> 8.79, so the head size 128
-// forward keeps the 8-wave plan.  DTA_PAIR_N1 = 0 (A/B builds) keeps 8 waves everywhere.
-#ifndef DTA_PAIR_N1
-#define DTA_PAIR_N1 1
-#endif
+// forward keeps the 8-wave plan.
 template <class E, int HS, int N, int DV = 2 * HS, bool NP = false>
 struct FwdPick {
   static constexpr int DVC = FwdChunk<N, DV, sizeof(E) == 2>::DVC;
@@ -743,7 +713,7 @@ struct FwdPick {
                              FwdCfg<E, HS, N, DVC, 8, false>::regs <= 280;
   static constexpr bool q4 = FwdCfg<E, HS, N, DVC, 4, false>::bytes <= LIM;
   // paired 4-wave plan with 64-key tiles and branch 0's Q in registers
-  static constexpr int QRH = (q8 && (N >= 2 || (DTA_PAIR_N1 && HS <= 96)) &&
+  static constexpr int QRH = (q8 && (N >= 2 || HS <= 96) &&
                               FwdCfg<E, HS, N, DVC, 4, false, 1>::bytes <= 80 * 1024) ? 1 : 0;
   static constexpr bool pair = !NP && QRH == 1 && q8 &&
                                 FwdCfg<E, HS, N, DVC, 4, false, QRH>::PAIR &&
@@ -762,22 +732,13 @@ struct FwdPick {
 // LDS accesses complete in order, so no wait sits between the write and the read.
 // val(d, g) returns the lane's 4 values of column block d, group g; rows >= nrows are not
 // stored.  dst: row 0, column 0 of the wave's tile; ld: row stride in OutT elements.
-#ifndef DTA_FWD_BOUNCE
-#define DTA_FWD_BOUNCE 1
-#endif
-#ifndef DTA_BWD_BOUNCE
-#define DTA_BWD_BOUNCE 1
-#endif
-// Non-temporal bounced stores (whole 256-byte row segments, unlike the per-lane 16-byte stores
-// that measured much slower NT in round 4): 1 = the fp32 ones -- the forward's O_i (537 MB at
-// cfg2, read back once by attn_dq) and the dV sums -- so they stop evicting the operands the next
-// kernels read from the Infinity Cache; 2 = every bounced store.  Step-interleaved A/B
-// (profiles/r06i_ab_bounce_nt.json): cfg2 fwd + dq + dK/dV 2.879 -> 2.838 ms (1) / 2.835 (2),
-// cfg3 N = 3 1.049 -> 1.034 / 1.037.  1 by default: the bf16 outputs (O, dQ, dK, dV) feed the
-// very next kernels of a training step (GroupLN, the projection GEMMs).
-#ifndef DTA_BOUNCE_NT
-#define DTA_BOUNCE_NT 1
-#endif
+// The fp32 bounced stores are non-temporal (whole 256-byte row segments, unlike the per-lane
+// 16-byte stores that measured much slower NT in round 4): the forward's O_i (537 MB at cfg2,
+// read back once by attn_dq) and the dV sums stop evicting the operands the next kernels read
+// from the Infinity Cache.  Step-interleaved A/B (profiles/r06i_ab_bounce_nt.json): cfg2 fwd +
+// dq + dK/dV 2.879 -> 2.838 ms, with every bounced store non-temporal 2.835; cfg3 N = 3 1.049 ->
+// 1.034 / 1.037.  The 16-bit ones stay plain: the bf16 outputs (O, dQ, dK, dV) feed the very next
+// kernels of a training step (GroupLN, the projection GEMMs).
 template <class OutT, int NDB, class Val>
 __device__ __forceinline__ void bounce_store(float* reg, int lane, Val&& val, OutT* dst, int64_t ld, int nrows) {
   const int r = lane & 31, hf = lane >> 5;
@@ -799,10 +760,7 @@ __device__ __forceinline__ void bounce_store(float* reg, int lane, Val&& val, Ou
       for (int k = 0; k < 8; ++k) {
         const int rr = k * 4 + (lane >> 4), c = lane & 15;
         const f32x4 v = *reinterpret_cast<const f32x4*>(reg + rr * 64 + ((c ^ (rr & 15)) << 2));
-        if (rr < nrows) {
-          if constexpr (DTA_BOUNCE_NT >= 1) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + rr * ld + h * 64 + c * 4));
-          else *reinterpret_cast<f32x4*>(dst + rr * ld + h * 64 + c * 4) = v;
-        }
+        if (rr < nrows) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + rr * ld + h * 64 + c * 4));
       }
     } else {
       typedef OutT v8 __attribute__((ext_vector_type(8)));
@@ -812,10 +770,7 @@ __device__ __forceinline__ void bounce_store(float* reg, int lane, Val&& val, Ou
         const f32x4 a = *reinterpret_cast<const f32x4*>(reg + rr * 64 + ((c ^ (rr & 15)) << 2));
         const f32x4 bq = *reinterpret_cast<const f32x4*>(reg + rr * 64 + (((c + 1) ^ (rr & 15)) << 2));
         const v8 v = {(OutT)a[0], (OutT)a[1], (OutT)a[2], (OutT)a[3], (OutT)bq[0], (OutT)bq[1], (OutT)bq[2], (OutT)bq[3]};
-        if (rr < nrows) {
-          if constexpr (DTA_BOUNCE_NT >= 2) __builtin_nontemporal_store(v, reinterpret_cast<v8*>(dst + rr * ld + h * 64 + c * 4));
-          else *reinterpret_cast<v8*>(dst + rr * ld + h * 64 + c * 4) = v;
-        }
+        if (rr < nrows) *reinterpret_cast<v8*>(dst + rr * ld + h * 64 + c * 4) = v;
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -878,7 +833,7 @@ void attn_fwd_kernel(FwdParams p) {
   static_assert(!SEQ || (N == 1 && QRH == 1 && DVC == 2 * HS && !DROP), "SEQ: N = 1 paired plans, whole dv");
   // the bounced epilogue (see bounce_store): 16-bit plans with whole 64-column passes, a
   // ring that holds a region per wave, fp32 O_i and 16-byte aligned outputs
-  constexpr bool BNC = DTA_FWD_BOUNCE && sizeof(E) == 2 && NDB % 2 == 0 &&
+  constexpr bool BNC = sizeof(E) == 2 && NDB % 2 == 0 &&
                        NS * (CF::nK + CF::nV) * (int)sizeof(E) >= NW * 8192;
   const bool bnc = BNC && !p.ob16 && t5_aligned16(p.obr, 4) && (nsp > 1 || t5_aligned16(p.o, sizeof(E)));
   const int nseq = SEQ ? p.bseq : 1;
@@ -931,19 +886,6 @@ void attn_fwd_kernel(FwdParams p) {
       }
   }
 
-  // FSEED (see below; the same condition as FAST): the register-resident Q_i pre-scaled by
-  // scale*log2e once, after the RoPE'd rows went to qrot; the LDS-resident ones after they land
-  constexpr bool FSEED_Q = DTA_FWD_SEED && DTA_FWD_FAST && sizeof(E) == 2 && !DROP && N <= 2 &&
-                           (CF::PAIR || CF::WPE >= 2);
-  if constexpr (FSEED_Q) {
-#pragma unroll
-    for (int i = 0; i < NQR; ++i)
-#pragma unroll
-      for (int s = 0; s < NSQ; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[i][s][j] = (E)((float)qf[i][s][j] * p.sl2);
-  }
-  bool q_lds_unscaled = FSEED_Q && N > NQR;
   const int kend = min(T, q0 + BM);
   const int ntiles = (kend + BN - 1) / BN;
   using KR = KvRing<E, HS, N, DVC, BN, NW>;
@@ -978,22 +920,9 @@ void attn_fwd_kernel(FwdParams p) {
   // or a non-finite score); fp16 saturates at 65504: 2^15.
   // (N <= 2 plans with two waves per SIMD: the one-wave 512-register plans and the hs = 32
   // N = 3 paired plan spill with it)
-  constexpr bool FAST = DTA_FWD_FAST && sizeof(E) == 2 && !DROP && N <= 2 && (CF::PAIR || CF::WPE >= 2);
+  constexpr bool FAST = sizeof(E) == 2 && !DROP && N <= 2 && (CF::PAIR || CF::WPE >= 2);
   constexpr float LSMAX = std::is_same<E, _Float16>::value ? 0x1p15f : 0x1p60f;
   float bad = 0.f;
-  // SEED (with FAST): Q_i are pre-scaled by scale*log2e once (registers and LDS), so scores come
-  // out of QK^T in log2 units, and on the fixed-reference tiles each branch's S accumulators
-  // start at -m by one extra MFMA (a ones fragment times the row constant split into hi + lo
-  // halves, as in attn_dq): P = exp2(S) needs no fma.  Entering those tiles each m moves to a value
-  // the two halves represent exactly, so the seeded tiles, the earlier ones and the LSE agree.
-  constexpr bool FSEED = DTA_FWD_SEED && FAST;
-  static_assert(FSEED == FSEED_Q, "FSEED_Q restates FAST's condition");
-  typename O::frag f_one = O::zero(), f_nm[FSEED ? N : 1];
-  if constexpr (FSEED) { if (hf == 0) { f_one[0] = (E)1.f; f_one[1] = (E)1.f; } }
-  auto mrep = [](float v) -> float {     // nearest value hi + lo (two E halves) represent
-    const E hi = (E)v;
-    return (float)hi + (float)(E)(v - (float)hi);
-  };
 
   // per-lane LDS read bases kept in registers across the loop (see attn_dkdv_kernel)
   int LrK = 0, LtV = 0;      // set per attempt, after the ring prologue
@@ -1019,42 +948,20 @@ void attn_fwd_kernel(FwdParams p) {
   };
   // P = exp2(S * scale*log2e - m), row sums (two chains), packed to the PV operand;
   // with dropout the row sum keeps every element and the PV operand only the kept ones
-  auto exp_pack = [&](int i, int k0, f32x16 (&sa)[NKB], frag (&pf)[NKB * SPB], bool seeded = false) -> float {
+  auto exp_pack = [&](int i, int k0, f32x16 (&sa)[NKB], frag (&pf)[NKB * SPB]) -> float {
     const float mi = m[i];
     float ls0 = 0.f, ls1 = 0.f;
-    // FSEED: scores already in log2 units (seeded tiles: already minus m)
-    auto arg = [&](float v) { return FSEED ? (seeded ? v : v - mi) : fmaf(v, p.sl2, -mi); };
-    if constexpr (DTA_FWD_PK && !FSEED) {
-      // the argument fmas and the two row-sum chains as packed pairs (v_pk_fma_f32 /
-      // v_pk_add_f32): element for element the scalar form's arithmetic, bitwise equal
-      f32x2 ls2 = f32x2{0.f, 0.f};
-      const f32x2 sl2v = f32x2{p.sl2, p.sl2}, nmv = f32x2{-mi, -mi};
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 a2 = __builtin_elementwise_fma(f32x2{sa[kb][r], sa[kb][r + 1]}, sl2v, nmv);
-          const float e0 = exp2_fast(a2[0]);
-          const float e1 = exp2_fast(a2[1]);
-          sa[kb][r] = e0;
-          sa[kb][r + 1] = e1;
-          ls2 += f32x2{e0, e1};
-        }
-      ls0 = ls2[0];
-      ls1 = ls2[1];
-    } else {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        const float e0 = exp2_fast(arg(sa[kb][r]));
-        const float e1 = exp2_fast(arg(sa[kb][r + 1]));
+        const float e0 = exp2_fast(fmaf(sa[kb][r], p.sl2, -mi));
+        const float e1 = exp2_fast(fmaf(sa[kb][r + 1], p.sl2, -mi));
         sa[kb][r] = e0;
         sa[kb][r + 1] = e1;
         ls0 += e0;
         ls1 += e1;
       }
-    }
     const float ls = ls0 + ls1;
     l[i] += ls;
     if constexpr (DROP) {
@@ -1082,13 +989,11 @@ void attn_fwd_kernel(FwdParams p) {
   auto softmax_branch = [&](int i, int k0, auto MASKED, f32x16 (&sa)[NKB], frag (&pf)[NKB * SPB], auto FASTT) {
     if constexpr (decltype(MASKED)::value) mask_scores(k0, sa);
     if constexpr (decltype(FASTT)::value) {
-      {
-        const float ls = exp_pack(i, k0, sa, pf, FSEED);
-        bad = (ls <= LSMAX) ? bad : 1.f;        // NaN / inf / past the operand range: re-run
-        return;
-      }
+      const float ls = exp_pack(i, k0, sa, pf);
+      bad = (ls <= LSMAX) ? bad : 1.f;        // NaN / inf / past the operand range: re-run
+      return;
     }
-    const float mx = wave_max_halves(row_max(sa)) * (FSEED ? 1.f : p.sl2);
+    const float mx = wave_max_halves(row_max(sa)) * p.sl2;
     if (__any(mx > m[i] + THR)) {
       const float mnew = fmaxf(m[i], mx);
       const float alpha = exp2_fast(m[i] - mnew);
@@ -1098,19 +1003,6 @@ void attn_fwd_kernel(FwdParams p) {
       for (int d = 0; d < NDB; ++d) acc[i][d] *= alpha;
     }
     exp_pack(i, k0, sa, pf);
-  };
-  // DTA_FWD_TR_EARLY (single-branch 16-bit plans without dropout -- the N = 2 plan spills with it --
-  // on the non-pipelined PV path): the first d-block's V^T
-  // reads of the PV product are issued after the last branch's QK^T chain, ahead of its softmax
-  // VALU, so their LDS latency hides behind it (16 more VGPRs live across it)
-  constexpr bool FTRE = DTA_FWD_TR_EARLY && N == 1 && sizeof(E) == 2 && !DROP && !(DTA_FWD_PIPE > 0 && NKB == 1 && NDB > 1);
-  lds64 rv0[NKB][4];        // (full size even when unused: referenced in a generic lambda)
-  auto issue_v0 = [&](int kt) {
-    if constexpr (FTRE) {
-      const unsigned vb = lds_addr(Vb + (kt % NS) * CF::nV);
-      const unsigned a0 = vb + LtV, a1 = vb + (LtV ^ 32);
-      sfor<NKB>([&](auto KB) { tr_issue<VI::ROWB, 32 * decltype(KB)::value>(rv0[decltype(KB)::value], a0, a1); });
-    }
   };
   // QK^T + online softmax of one key tile for every branch, P packed as the PV B operand
   auto phase_a = [&](int kt, auto MASKED, frag (&pf)[N][NKB * SPB], auto FASTT) {
@@ -1128,8 +1020,7 @@ void attn_fwd_kernel(FwdParams p) {
         const char* kbase = reinterpret_cast<const char*>(Ki);
         const char* qbase = reinterpret_cast<const char*>(Qs + (i >= NQR ? i - NQR : 0) * BM * HSP) + wave * 32 * QI::ROWB;
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-          sa[i][kb] = (FSEED && decltype(FASTT)::value) ? O::mma(f_one, f_nm[FSEED ? i : 0], f32x16{}) : f32x16{};
+        for (int kb = 0; kb < NKB; ++kb) sa[i][kb] = f32x16{};
         if constexpr (NSQ * (NKB + 1) <= 12 && QRH == 0) {
           // every operand read of this branch's S^T issued ahead of its MFMA chain,
           // so the chain waits on the LDS latency once instead of per k-step
@@ -1150,7 +1041,7 @@ void attn_fwd_kernel(FwdParams p) {
           if (i < NQR) __builtin_amdgcn_sched_group_barrier(0x100, NSQ * NKB, 0);
           else __builtin_amdgcn_sched_group_barrier(0x100, NSQ * (NKB + 1), 0);
           __builtin_amdgcn_sched_group_barrier(0x008, NSQ * NKB, 0);
-        } else if constexpr (DTA_FWD_PIPE > 0 && QI::ROWB == KI::ROWB && NKB == 1) {
+        } else if constexpr (QI::ROWB == KI::ROWB && NKB == 1) {
           // operand reads DTA_FWD_PIPE reads ahead of the MFMAs (see s_chain_pipe); 32-key
           // tiles only: with 64-key tiles (cfg2) the paired plan sits at 252 VGPRs and the
           // pipelined chain measured slower (fwd 0.954 -> 1.008 ms), cfg5 0.97x
@@ -1186,7 +1077,6 @@ void attn_fwd_kernel(FwdParams p) {
           }
         }
       }
-      if (FTRE && i == N - 1) issue_v0(kt);
       softmax_branch(i, k0, MASKED, sa[i], pf[i], FASTT);
     }
   };
@@ -1195,7 +1085,7 @@ void attn_fwd_kernel(FwdParams p) {
     const E* Vc = Vb + (kt % NS) * CF::nV;
     // the dropout plans spill (up to 128 B/lane): compiler-tracked V^T reads (see tr_load)
     constexpr bool SPILLS = DROP;
-    if constexpr (sizeof(E) == 2 && DTA_FWD_PIPE > 0 && NKB == 1 && NDB > 1 && !SPILLS) {
+    if constexpr (sizeof(E) == 2 && NKB == 1 && NDB > 1 && !SPILLS) {
       // the next d-block's V^T fragments read while this one's MFMAs run (32-key tiles:
       // 8 more VGPRs)
       const unsigned vb = lds_addr(Vc);
@@ -1227,18 +1117,6 @@ void attn_fwd_kernel(FwdParams p) {
         constexpr int d = decltype(D)::value;
         lds64 r[NKB][4];
         const unsigned a0 = vb + (Lv ^ (64 * d)), a1 = vb + (Lv ^ (64 * d + 32));
-        if constexpr (FTRE && d == 0) {
-          lgkm_pin<NKB>(rv0);
-#pragma unroll
-          for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-              const frag va = tr_frag<E>(rv0[kb], s);
-#pragma unroll
-              for (int i = 0; i < N; ++i) acc[i][d] = O::mma(va, pf[i][kb * 2 + s], acc[i][d]);
-            }
-          return;
-        }
         if constexpr (SPILLS) {
           sfor<NKB>([&](auto KB) { tr_load<VI::ROWB, 32 * decltype(KB)::value>(r[decltype(KB)::value], a0, a1); });
         } else {
@@ -1283,7 +1161,6 @@ void attn_fwd_kernel(FwdParams p) {
     st.lap<7>();
     if (kt + NS - 1 < ntiles) stage_kv(kt + NS - 1, (kt + NS - 1) % NS);
     st.lap<0>();
-    if constexpr (DTA_FWD_IGLP >= 0) __builtin_amdgcn_iglp_opt(DTA_FWD_IGLP >= 0 ? DTA_FWD_IGLP : 0);   // A/B: LLVM's MFMA / LDS interleave strategy
     if (live) {
       frag pf[N][NKB * SPB];
       phase_a(kt, MASKED, pf, FASTT);
@@ -1312,11 +1189,6 @@ void attn_fwd_kernel(FwdParams p) {
       lds_barrier();
       qrot_pending = false;
     }
-    if (q_lds_unscaled) {                    // FSEED: the LDS-resident Q_i, once
-      scale_lds<E, NTHR>(Qs, CF::nQ, p.sl2, tid);
-      lds_barrier();
-      q_lds_unscaled = false;
-    }
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       m[i] = -INFINITY;
@@ -1332,22 +1204,6 @@ void attn_fwd_kernel(FwdParams p) {
     for (int kt = 0; kt < min(nfull, kslow); ++kt) step(kt, std::false_type{}, std::false_type{});
     for (int kt = nfull; kt < kslow; ++kt) step(kt, std::true_type{}, std::false_type{});
     if constexpr (FAST) {
-      if constexpr (FSEED) {
-        // the fixed reference moves to the nearest value the seed's two E halves represent (the
-        // first tile's sums and accumulators follow it, a factor of 1 + O(2^-16)); one the halves
-        // cannot hold (fp16 beyond 65504) sends the workgroup to the exact per-tile-maximum re-run
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-          const float mr = mrep(m[i]);
-          if (!(fabsf(mr) < INFINITY)) bad = 1.f;
-          const float a = (fabsf(mr) < INFINITY) ? exp2_fast(m[i] - mr) : 1.f;
-          l[i] *= a;
-#pragma unroll
-          for (int d = 0; d < NDB; ++d) acc[i][d] *= a;
-          m[i] = (fabsf(mr) < INFINITY) ? mr : m[i];
-          f_nm[i] = seed_frag<E>(-m[i], hf);
-        }
-      }
       for (int kt = kslow; kt < nfull; ++kt) step(kt, std::false_type{}, std::true_type{});
       for (int kt = max(kslow, nfull); kt < ntiles; ++kt) step(kt, std::true_type{}, std::true_type{});
     }
@@ -1372,7 +1228,6 @@ void attn_fwd_kernel(FwdParams p) {
   st.flush(p.stamps, lin * NW + wave, lane);
 
   if (!SEQ && !wave_live) return;
-  if (DTA_EPI_SKIP == 1 && p.T != -7) return;
   if (bnc) {
     if (wave_live) {
       float inv[N];
@@ -1441,7 +1296,7 @@ void attn_fwd_kernel(FwdParams p) {
       for (int i = 0; i < N; ++i) {
         const float a0 = acc[i][d][4 * g + 0] * inv[i], a1 = acc[i][d][4 * g + 1] * inv[i];
         const float a2 = acc[i][d][4 * g + 2] * inv[i], a3 = acc[i][d][4 * g + 3] * inv[i];
-        if (DTA_EPI_SKIP != 2 || p.T == -7) store_ob4(p.obr.p, gob + i * p.obr.si + e, p.ob16, a0, a1, a2, a3);
+        store_ob4(p.obr.p, gob + i * p.obr.si + e, p.ob16, a0, a1, a2, a3);
         o0 = fmaf(coef[i], a0, o0); o1 = fmaf(coef[i], a1, o1);
         o2 = fmaf(coef[i], a2, o2); o3 = fmaf(coef[i], a3, o3);
       }
@@ -1498,54 +1353,29 @@ struct DqCfg {
 // SIMD (Q of all branches in registers, 160 AGPRs).  In the paired layout with 32-key
 // tiles (branch 0's Q in registers, branches 1-2 in LDS, 72 KB, 252 VGPRs, no spill) it is
 // faster: one-process A/B (profiles/r05g_ab_dq_pair3.json) cfg3 B=16 H=6 T=2048 dQ 0.414 ->
-// 0.379 ms, B=8 H=16 T=4096 1.683 -> 1.329 ms.  DTA_DQ_PAIR3 = 0 (A/B builds) keeps one wave.
+// 0.379 ms, B=8 H=16 T=4096 1.683 -> 1.329 ms.
 #ifndef DTA_DQ_EXPG
 #define DTA_DQ_EXPG 4            // exps per group ahead of their products in the dQ softmax (r05u: 1 -> 4, cfg2 dQ 0.888 -> 0.867 ms)
 #endif
-#ifndef DTA_DQ_PAIR3
-#define DTA_DQ_PAIR3 1
-#endif
-#ifndef DTA_DQ_TR_EARLY
-#define DTA_DQ_TR_EARLY 0        // A/B: dQ's first d-block transposed K_i reads issued before the softmax VALU
-#endif
-#ifndef DTA_DKDV_TR_EARLY
-#define DTA_DKDV_TR_EARLY 0      // A/B: dK/dV's transposed Q_i reads issued before the softmax VALU
-#endif
-#ifndef DTA_DQ_PK
-#define DTA_DQ_PK 0              // A/B: dQ's dS math as packed fp32 pairs (v_pk_*): 120 -> 78 VALU issues per step, dq +1% (r06p): off
-#endif
-#ifndef DTA_DKDV_PK
-#define DTA_DKDV_PK 0            // A/B: dK/dV's dS / dV-operand math as packed fp32 pairs (v_pk_*): 123 -> 101 VALU issues, dK/dV +2.8% (r06p): off
-#endif
-#ifndef DTA_DKDV_CFOLD
-#define DTA_DKDV_CFOLD 1         // 0: never build the |c_i|-folded dK/dV instantiations (lse_c ignored)
-#endif
-#ifndef DTA_DQ_EARLY_RING
-#define DTA_DQ_EARLY_RING 0      // A/B: the K/V ring's first stages issued before the delta_i prologue
-#endif
-#ifndef DTA_DQ_B32_N2
-#define DTA_DQ_B32_N2 0          // A/B: the paired N = 2 dQ plan with 32-key tiles
-#endif
+static_assert(DTA_DQ_EXPG >= 1 && 16 % DTA_DQ_EXPG == 0, "DTA_DQ_EXPG: a divisor of the 16 rows a lane holds");
 template <class E, int HS, int N, int DV = 2 * HS, bool NP = false>
 struct DqPick {
   static constexpr int LIM = 160 * 1024;
   static constexpr bool q8 = sizeof(E) == 2 && DqCfg<E, HS, N, DV, 8, false>::bytes <= LIM;
   // paired 4-wave plan with 64-key tiles and branch 0's Q in registers
-  static constexpr int QRH = (q8 && (N >= 2 || DTA_PAIR_N1) &&
-                              DqCfg<E, HS, N, DV, 4, false, 1>::bytes <= 80 * 1024) ? 1 : 0;
+  static constexpr int QRH = (q8 && DqCfg<E, HS, N, DV, 4, false, 1>::bytes <= 80 * 1024) ? 1 : 0;
   // (head size >= 64: the hs = 32, N = 3 paired plan spills)
   static constexpr bool pair64 = !NP && QRH == 1 && q8 && HS >= 64 &&
                                  DqCfg<E, HS, N, DV, 4, false, QRH>::bytes <= 80 * 1024;
   // N >= 3 at head size 64, where no 8-wave plan fits: the paired layout with 32-key
-  // tiles (branch 0's Q in registers) instead of one wave per SIMD (DTA_DQ_PAIR3)
-  static constexpr bool pair32 = DTA_DQ_PAIR3 && !NP && !pair64 && sizeof(E) == 2 && N >= 3 && HS == 64 &&
+  // tiles (branch 0's Q in registers) instead of one wave per SIMD
+  static constexpr bool pair32 = !NP && !pair64 && sizeof(E) == 2 && N >= 3 && HS == 64 &&
                                  DqCfg<E, HS, N, DV, 4, false, 1, true>::bytes <= 80 * 1024;
   static constexpr bool pair = pair64 || pair32;
   static constexpr int NW = pair ? 4 : (q8 ? 8 : (sizeof(E) == 2 ? 4 : 2));
   static constexpr bool QREG = pair ? false : !q8;
   static constexpr int QH = pair ? 1 : 0;
-  static constexpr bool B32 = pair32 || (DTA_DQ_B32_N2 && pair64 && N == 2) ||
-                              DqCfg<E, HS, N, DV, NW, QREG, QH>::bytes > LIM;   // 32-key tiles
+  static constexpr bool B32 = pair32 || DqCfg<E, HS, N, DV, NW, QREG, QH>::bytes > LIM;   // 32-key tiles
   static constexpr bool ok = DqCfg<E, HS, N, DV, NW, QREG, QH, B32>::bytes <= LIM;
 };
 
@@ -1613,17 +1443,11 @@ void attn_dq_kernel(BwdParams p) {
   };
 
   // (head size 128 at N >= 3 spills further with the seed fragments: it keeps the fmas)
-  constexpr bool SEED = DTA_DQ_SEED && std::is_same<E, __bf16>::value && !DROP && SRD && !(HS >= 128 && N >= 3);
+  constexpr bool SEED = std::is_same<E, __bf16>::value && !DROP && SRD && !(HS >= 128 && N >= 3);
   // plans that spill (16-bit head size 128 at N >= 3: 84-508 B/lane of scratch; dropout
   // plans: up to 532 B/lane) read LDS only through compiler-tracked loads: no asm read
   // whose destination the allocator could spill before it lands (see tr_load)
   constexpr bool SPILLS = sizeof(E) == 2 && (DROP || (HS >= 128 && N >= 3) || (HS >= 192 && N >= 2));
-  // DTA_DQ_EARLY_RING: the ring's first stages are issued before the per-row loads and the
-  // delta_i reduction below, so their DMA overlaps the O_i reads instead of following them
-  constexpr bool EARLY = DTA_DQ_EARLY_RING && SRD;
-  if constexpr (EARLY)
-    for (int j = 0; j < NS - 1; ++j)
-      if (j < ntiles) stage_kv(j, j);
   // ---- per-row operands in registers: Q_i and dO rows (B operands), LSE, delta
   frag qf[NQR > 0 ? NQR : 1][NQR > 0 ? NSQ : 1], df[NSV];
   float coef[N], lse[N], del[N];
@@ -1674,7 +1498,7 @@ void attn_dq_kernel(BwdParams p) {
     // dropout -delta_h (its dP accumulator's seed) at each dK/dV group's first branch h and
     // delta_h - delta_i after it -- h = 0 (this group), or the dK/dV grouping's starts
     // (p.kstarts, this launch holding every branch); with dropout delta_i
-    const bool kstart = i == 0 || (DTA_DQ_KSTARTS && ((p.kstarts >> i) & 1));
+    const bool kstart = i == 0 || ((p.kstarts >> i) & 1);
     if (kstart) dhead = d;
     if (rowok && hf == 0) p.delta[rs + i * bstride] = DROP ? d : (kstart ? -d : dhead - d);
     // d(coef)[h][i] = sum over rows of delta_i: one atomic per wave
@@ -1696,10 +1520,8 @@ void attn_dq_kernel(BwdParams p) {
   }
   const int tile_pieces = SRD ? KR::pieces(wave)
                               : N * stage_pieces<E, HSP, BN, HS, NW>(wave) + stage_pieces<E, DVP, BN, DV, NW>(wave);
-  if constexpr (!EARLY)
-    for (int j = 0; j < NS - 1; ++j)
-      if (j < ntiles) stage_kv(j, j);
-  // (EARLY: younger loads and stores follow the ring's pieces, so this waits for at least them)
+  for (int j = 0; j < NS - 1; ++j)
+    if (j < ntiles) stage_kv(j, j);
   wait_vm(tile_pieces * max(0, min(NS - 1, ntiles) - 1));
   lds_barrier();
   // SEED: the LDS-resident Q_i rows pre-scaled by sl2 once; the seed fragments
@@ -1758,7 +1580,6 @@ void attn_dq_kernel(BwdParams p) {
     const int buf = kt % NS;
     if (kt + NS - 1 < ntiles) stage_kv(kt + NS - 1, (kt + NS - 1) % NS);
     st.lap<0>();
-    if constexpr (DTA_DQ_IGLP >= 0) __builtin_amdgcn_iglp_opt(DTA_DQ_IGLP >= 0 ? DTA_DQ_IGLP : 0);   // A/B: LLVM's MFMA / LDS interleave strategy
     const int k0 = kt * BN;
     if (wave_live && k0 <= qw0 + 31) {
       const E* Kc = Kb + buf * CF::nK;
@@ -1774,7 +1595,7 @@ void attn_dq_kernel(BwdParams p) {
           const char* vbase = reinterpret_cast<const char*>(Vc);
 #pragma unroll
           for (int kb = 0; kb < NKB; ++kb) dp[kb] = SEED ? O::mma(f_one, f_dp, f32x16{}) : f32x16{};
-          if constexpr (XA && DTA_DQ_PIPE > 0 && !SPILLS) {
+          if constexpr (XA && !SPILLS) {
             // V fragments read DTA_DQ_PIPE MFMAs ahead (k-step major, key block minor)
             constexpr int NIT = NSV * NKB, D = DTA_DQ_PIPE;
             i32x4 vb[D + 1];
@@ -1814,7 +1635,7 @@ void attn_dq_kernel(BwdParams p) {
           constexpr int i = decltype(I_)::value;
           const E* Ki = Kc + i * BN * HSP;
           f32x16 sa[NKB];
-          if constexpr (XA && DTA_DQ_PIPE > 0 && !SPILLS) {
+          if constexpr (XA && !SPILLS) {
             // S'_i chain with its operand reads DTA_DQ_PIPE reads ahead of the MFMAs
             constexpr int QL = i >= NQR ? 1 : 0;
             constexpr int KOFF = i * BN * HSP * (int)sizeof(E), QOFF = (i >= NQR ? i - NQR : 0) * BM * QP * (int)sizeof(E);
@@ -1857,16 +1678,6 @@ void attn_dq_kernel(BwdParams p) {
               }
             }
           }
-          // DTA_DQ_TR_EARLY: the first d-block's transposed K_i reads of dQ_i issued here, ahead
-          // of the softmax VALU below (16 more VGPRs live across it)
-          constexpr bool TRE = DTA_DQ_TR_EARLY && sizeof(E) == 2 && !SPILLS;
-          lds64 rk0[NKB][4];      // (full size even when unused: referenced in a generic lambda)
-          if constexpr (TRE) {
-            const unsigned kbse = lds_addr(Ki);
-            const unsigned a0 = XA ? tK + (unsigned)(i * BN * HSP * (int)sizeof(E)) : kbse + LtK;
-            const unsigned a1 = XA ? (tK ^ 32) + (unsigned)(i * BN * HSP * (int)sizeof(E)) : kbse + (LtK ^ 32);
-            sfor<NKB>([&](auto KB) { tr_issue<KI::ROWB, 32 * decltype(KB)::value>(rk0[decltype(KB)::value], a0, a1); });
-          }
           // dS^T = c_i P^T (dP^T - delta_i) = P^T * (c_i dP^T - c_i delta_i)
           const float li = lse[i], ci = coef[i], cdi = coef[i] * del[i];
           const int lim = min(qrow, T - 1) - k0 - 4 * hf;
@@ -1887,22 +1698,10 @@ void attn_dq_kernel(BwdParams p) {
                   if constexpr (MASK) arg = (kb * 32 + (r & 3) + 8 * (r >> 2) > lim) ? -INFINITY : arg;
                   pr[u] = exp2_fast(arg);
                 }
-                if constexpr (DTA_DQ_PK && DTA_DQ_EXPG % 2 == 0) {
-                  // two rows per v_pk_mul_f32 / v_pk_add_f32 (same fp32 arithmetic per element)
 #pragma unroll
-                  for (int u = 0; u < DTA_DQ_EXPG; u += 2) {
-                    const int r = r0 + u;
-                    const f32x2 p2 = f32x2{pr[u], pr[u + 1]}, d2 = f32x2{dp[kb][r], dp[kb][r + 1]};
-                    const f32x2 s2 = i == 0 ? p2 * d2 : p2 * (d2 + f32x2{dd, dd});
-                    sa[kb][r] = s2[0];
-                    sa[kb][r + 1] = s2[1];
-                  }
-                } else {
-#pragma unroll
-                  for (int u = 0; u < DTA_DQ_EXPG; ++u) {
-                    const int r = r0 + u;
-                    sa[kb][r] = i == 0 ? pr[u] * dp[kb][r] : pr[u] * (dp[kb][r] + dd);
-                  }
+                for (int u = 0; u < DTA_DQ_EXPG; ++u) {
+                  const int r = r0 + u;
+                  sa[kb][r] = i == 0 ? pr[u] * dp[kb][r] : pr[u] * (dp[kb][r] + dd);
                 }
               }
           } else {
@@ -1931,15 +1730,6 @@ void attn_dq_kernel(BwdParams p) {
               const unsigned a0 = XA ? (tK ^ (64 * d)) + (unsigned)(i * BN * HSP * (int)sizeof(E)) : kbse + (Lk ^ (64 * d));
               const unsigned a1 = XA ? (tK ^ (64 * d + 32)) + (unsigned)(i * BN * HSP * (int)sizeof(E))
                                      : kbse + (Lk ^ (64 * d + 32));
-              if constexpr (TRE && d == 0) {
-                lgkm_pin<NKB>(rk0);
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                  dq[i][d] = O::mma(tr_frag<E>(rk0[kb], 0), O::template pack<0>(sa[kb]), dq[i][d]);
-                  dq[i][d] = O::mma(tr_frag<E>(rk0[kb], 1), O::template pack<1>(sa[kb]), dq[i][d]);
-                }
-                return;
-              }
               if constexpr (SPILLS) {
                 sfor<NKB>([&](auto KB) { tr_load<KI::ROWB, 32 * decltype(KB)::value>(r[decltype(KB)::value], a0, a1); });
               } else {
@@ -1977,9 +1767,8 @@ void attn_dq_kernel(BwdParams p) {
   st.flush(p.stamps, lin * NW + wave, lane);
 
   if (qw0 >= T) return;
-  if (DTA_EPI_SKIP == 1 && p.T != -7) return;
   // bounced epilogue (see bounce_store; the ring is idle): whole-row store instructions
-  constexpr bool BNC = DTA_BWD_BOUNCE && sizeof(E) == 2 && NHB % 2 == 0 && CF::bytes >= NW * 8192;
+  constexpr bool BNC = sizeof(E) == 2 && NHB % 2 == 0 && CF::bytes >= NW * 8192;
   if constexpr (BNC) {
     if (OUTF32 || t5_aligned16(p.dq, sizeof(E))) {
       float* reg = reinterpret_cast<float*>(smem) + wave * 2048;
@@ -2101,10 +1890,8 @@ struct TileRing {
       } else {
         if (j < PQ) buf_lds16(bq, nq, st0 + j * 1024, off[u]);
         else if (j < PQ + PD) buf_lds16(bd, nd, st0 + OFF_D + (j - PQ) * 1024, off[u]);
-#ifndef DTA_DKDV_NOROWS_PROBE
         else if (j < PQ + PD + PL) buf_lds4(lse + q0, nl, st0 + OFF_L + (j - PQ - PD) * 256, off[u]);
         else if (j < NPC) buf_lds4(delta + q0, nl, st0 + OFF_G + (j - PQ - PD - PL) * 256, off[u]);
-#endif
       }
     });
   }
@@ -2334,7 +2121,6 @@ void attn_dkdv_kernel(BwdParams p) {
     const int q0 = kb0 + t * BQ;
     if (t + NS - 1 < ntiles) stage_q(q0 + (NS - 1) * BQ, (t + NS - 1) % NS);
     st.lap<0>();
-    if constexpr (DTA_DKDV_IGLP >= 0) __builtin_amdgcn_iglp_opt(DTA_DKDV_IGLP >= 0 ? DTA_DKDV_IGLP : 0);   // A/B: LLVM's MFMA / LDS interleave strategy
     if (wave_keys && q0 + 31 >= kw0) {
       const char* sg = ringb + buf * RG::SB;
       const E* Qc = SRD ? reinterpret_cast<const E*>(sg) : Qb + buf * N * BQ * HSP;
@@ -2423,21 +2209,7 @@ void attn_dkdv_kernel(BwdParams p) {
           for (int s = 0; s < NSQ; ++s)
             sa = O::mma(QI::row(Qi, c32, s, hf), KI::row(Ks + i * BK * KP, wave * 32 + c32, s, hf), sa);
         }
-        // DTA_DKDV_TR_EARLY: the transposed Q_i reads of dK_i issued here, ahead of the softmax
-        // VALU below, so their LDS latency hides behind it (16 more VGPRs live across it)
-        constexpr bool TRE = DTA_DKDV_TR_EARLY && DK && sizeof(E) == 2 && !SPILLS;
-        lds64 rq[TRE ? NHB : 1][4];
-        if constexpr (TRE) {
-          const unsigned qb = lds_addr(Qi);
-          const int Lq = LtQ;
-          sfor<NHB>([&](auto D) {
-            constexpr int d = decltype(D)::value;
-            if constexpr (XA) tr_issue<QI::ROWB, 0>(rq[d], (tQ ^ (64 * d)) + i * RG::QB, (tQ ^ (64 * d + 32)) + i * RG::QB);
-            else tr_issue<QI::ROWB, 0>(rq[d], qb + (Lq ^ (64 * d)), qb + (Lq ^ (64 * d + 32)));
-          });
-        }
         // sa[r] = S'_i[q0 + rowof(r)][krow] - LSE; rows 4g..4g+3 of a lane are consecutive
-        constexpr bool PK = DTA_DKDV_PK && !DROP && DK && CFOLD;   // (the unfolded SRD plan spills 18 VGPRs with it)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           f32x4 d4 = f32x4{};
@@ -2456,43 +2228,13 @@ void attn_dkdv_kernel(BwdParams p) {
               const float mk = drop_mul(dkey[i], q0 + (r & 3) + 8 * (r >> 2) + 4 * hf, krow, p.drop_thr, p.drop_scale);
               if constexpr (DVV) pc[r] = fmaf(coef[i] * mk, pr, pc[r]);
               if constexpr (DK) sa[r] = pr * fmaf(mk, dpa[r], -d4[j]);
-            } else if constexpr (PK) {
-              sa[r] = pr;                 // the pair math below, two rows per packed op
             } else {
               if constexpr (DVV) pc[r] = i == 0 ? (CFOLD ? pr : wv[0] * pr) : fmaf(wv[i], pr, pc[r]);
               if constexpr (DK) sa[r] = i == 0 ? pr * dpa[r] : pr * (dpa[r] + d4[j]);
             }
           }
-          if constexpr (PK) {
-            // v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: two rows per VALU issue (the same
-            // fp32 arithmetic per element, so results are bitwise those of the scalar form)
-#pragma unroll
-            for (int j = 0; j < 4; j += 2) {
-              const int r = 4 * g + j;
-              const f32x2 pr2 = f32x2{sa[r], sa[r + 1]};
-              const f32x2 dp2 = f32x2{dpa[r], dpa[r + 1]};
-              if constexpr (DVV) {
-                f32x2 pc2 = f32x2{pc[r], pc[r + 1]};
-                if (i == 0) pc2 = CFOLD ? pr2 : f32x2{wv[0], wv[0]} * pr2;
-                else pc2 = __builtin_elementwise_fma(f32x2{wv[i], wv[i]}, pr2, pc2);
-                pc[r] = pc2[0]; pc[r + 1] = pc2[1];
-              }
-              f32x2 s2;
-              if (i == 0) s2 = pr2 * dp2;
-              else s2 = pr2 * (dp2 + f32x2{d4[j], d4[j + 1]});
-              sa[r] = s2[0]; sa[r + 1] = s2[1];
-            }
-          }
         }
-        if constexpr (TRE) {
-          lgkm_pin<NHB>(rq);
-          const frag p0 = O::template pack<0>(sa), p1 = O::template pack<1>(sa);
-#pragma unroll
-          for (int d = 0; d < NHB; ++d) {
-            dk[i][d] = O::mma(tr_frag<E>(rq[d], 0), p0, dk[i][d]);
-            dk[i][d] = O::mma(tr_frag<E>(rq[d], 1), p1, dk[i][d]);
-          }
-        } else if constexpr (DK) {
+        if constexpr (DK) {
           if constexpr (sizeof(E) == 2) {
             const unsigned qb = lds_addr(Qi);
             const int Lq = LtQ;
@@ -2577,10 +2319,9 @@ void attn_dkdv_kernel(BwdParams p) {
   st.flush(p.stamps, lin * NW + wave, lane);
 
   if (!wave_keys) return;
-  if (DTA_EPI_SKIP == 1 && p.T != -7) return;
   // bounced epilogue (see bounce_store; the ring and the K_i rows are idle): dK, and dV
   // unless it adds to an earlier branch group's partial
-  constexpr bool BNC = DTA_BWD_BOUNCE && sizeof(E) == 2 && (!DK || NHB % 2 == 0) && (!DVV || NVB % 2 == 0) &&
+  constexpr bool BNC = sizeof(E) == 2 && (!DK || NHB % 2 == 0) && (!DVV || NVB % 2 == 0) &&
                        CF::bytes >= NW * 8192;
   if constexpr (BNC) {
     float* g32 = p.dv32 ? p.dv32 + (((int64_t)b * p.T + kw0) * p.H + hh) * p.DV : nullptr;
@@ -2746,27 +2487,19 @@ __global__ __launch_bounds__(256) void branch_combine_kernel(FwdParams p, Combin
 }
 
 // Branch-split forward policy: workgroups that hold ONE branch over the whole dv instead
-// of all N branches over a dv chunk.  Auto (DTA_FWD_BSPLIT unset / -1): wherever the
+// of all N branches over a dv chunk, wherever the
 // N-branch plan splits dv into chunks (each chunk redoes every branch's QK^T and
 // softmax: head size 128 at N = 2, cfg5; N = 4 at head size 64, cfg3) or runs one wave
 // per SIMD (N = 3 at head size 64, cfg3).  One-process A/B (profiles/r03_bsplit_ab.json):
 // cfg5 fwd 20.54 -> 12.66 ms, cfg3 N=4 0.744 -> 0.485, N=3 0.409 -> 0.361; cfg2's
-// paired N = 2 plan stays (split: 0.999 -> 1.126).  A/B builds: the macro DTA_FWD_BSPLIT = 0
-// builds no split at all, 1 also splits the non-auto plans (the product build is -1).
-#ifndef DTA_FWD_BSPLIT
-#define DTA_FWD_BSPLIT -1
-#endif
+// paired N = 2 plan stays (split: 0.999 -> 1.126).
 // Sequential-branch forward (SEQ kernels): where the N-branch forward runs branch-split and
 // the single-branch plan is the paired one with the whole dv in one workgroup, the N
 // branches of a query block run one after another in one workgroup, which forms O itself
-// instead of a combine pass re-reading every fp32 O_i (DTA_FWD_SEQ = 0 in A/B builds: the
-// branch-split workgroups plus branch_combine_kernel).
-#ifndef DTA_FWD_SEQ
-#define DTA_FWD_SEQ 1
-#endif
+// instead of a combine pass re-reading every fp32 O_i.
 template <class E, int HS, int DV, bool DROP>
 constexpr bool fwd_seq_ok() {
-  return DTA_FWD_SEQ && !DROP && sizeof(E) == 2 && DV == 2 * HS && FwdPick<E, HS, 1, DV, DROP>::pair &&
+  return !DROP && sizeof(E) == 2 && DV == 2 * HS && FwdPick<E, HS, 1, DV, DROP>::pair &&
          FwdPick<E, HS, 1, DV, DROP>::DVC == DV;
 }
 
@@ -2788,51 +2521,44 @@ int launch_fwd_t(const FwdParams& p, hipStream_t st) {
   constexpr int DVC = FP::DVC, NW = FP::NW;
   constexpr int QH = FP::QH;
   constexpr int bytes = FwdCfg<E, HS, N, DVC, NW, FP::QREG, QH>::bytes;
-  // auto: the N-branch plan splits dv, or (16-bit, head size >= 64) it is not the paired
-  // two-workgroups-per-CU plan (N >= 3, head size 96 / 128: one wave per SIMD).  Auto
-  // plans always split (their N-branch kernel is not built); an A/B build with
-  // DTA_FWD_BSPLIT = 1 also splits the others.
-  constexpr bool CAN = N >= 2 && Plan<E, HS, 1, PL::DV>::ok;
-  constexpr bool AUTO = CAN && DTA_FWD_BSPLIT != 0 &&
-                        (DVC < PL::DV || (sizeof(E) == 2 && HS >= 64 && !FwdPick<E, HS, N, PL::DV>::pair));
-  if constexpr (CAN) {
-    if (AUTO || DTA_FWD_BSPLIT > 0) {
-      FwdParams q = p;
-      if constexpr (fwd_seq_ok<E, HS, PL::DV, DROP>()) {
-        q.bseq = N;
-        return launch_fwd_t<E, HS, 1, DV_, DROP>(q, st);
-      }
-      q.bsplit = N;
-      if (int e = launch_fwd_t<E, HS, 1, DV_, DROP>(q, st)) return e;
-      const int64_t n = (int64_t)p.B * p.T * p.H * (PL::DV / (16 / (int)sizeof(E)));
-      if (n >= (1ll << 31)) return -2;
-      hipLaunchKernelGGL((branch_combine_kernel<E, N>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p,
-                         combine_div(p, (int)sizeof(E)));
-      return (int)hipGetLastError();
+  // branch-split where the N-branch plan splits dv, or (16-bit, head size >= 64) is not the
+  // paired two-workgroups-per-CU plan (N >= 3, head size 96 / 128: one wave per SIMD).  Such
+  // plans always split: their N-branch kernel is not built.
+  constexpr bool SPLIT = N >= 2 && Plan<E, HS, 1, PL::DV>::ok &&
+                         (DVC < PL::DV || (sizeof(E) == 2 && HS >= 64 && !FwdPick<E, HS, N, PL::DV>::pair));
+  if constexpr (SPLIT) {
+    FwdParams q = p;
+    if constexpr (fwd_seq_ok<E, HS, PL::DV, DROP>()) {
+      q.bseq = N;
+      return launch_fwd_t<E, HS, 1, DV_, DROP>(q, st);
     }
-  }
-  if constexpr (AUTO) {
-    return -2;       // unreachable
+    q.bsplit = N;
+    if (int e = launch_fwd_t<E, HS, 1, DV_, DROP>(q, st)) return e;
+    const int64_t n = (int64_t)p.B * p.T * p.H * (PL::DV / (16 / (int)sizeof(E)));
+    if (n >= (1ll << 31)) return -2;
+    hipLaunchKernelGGL((branch_combine_kernel<E, N>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p,
+                       combine_div(p, (int)sizeof(E)));
+    return (int)hipGetLastError();
   } else {
-  const int nsp = (N == 1 && p.bsplit > 1) ? p.bsplit : 1;
-  dim3 grid((p.T + NW * 32 - 1) / (NW * 32), p.H * nsp * (PL::DV / DVC), p.B);
-  auto run = [&](auto SRDV) -> int {
-    auto go = [&](auto K) -> int {
-      if (int e = set_smem(K, bytes)) return e;
-      hipLaunchKernelGGL(K, grid, dim3(NW * 64), bytes, st, p);
-      return 0;
+    const int nsp = (N == 1 && p.bsplit > 1) ? p.bsplit : 1;
+    dim3 grid((p.T + NW * 32 - 1) / (NW * 32), p.H * nsp * (PL::DV / DVC), p.B);
+    auto run = [&](auto SRDV) -> int {
+      auto go = [&](auto K) -> int {
+        if (int e = set_smem(K, bytes)) return e;
+        hipLaunchKernelGGL(K, grid, dim3(NW * 64), bytes, st, p);
+        return 0;
+      };
+      if constexpr (N == 1 && fwd_seq_ok<E, HS, PL::DV, DROP>())
+        if (p.bseq > 1) return go(attn_fwd_kernel<E, HS, N, DVC, NW, FP::QREG, decltype(SRDV)::value, DROP, QH, true>);
+      return go(attn_fwd_kernel<E, HS, N, DVC, NW, FP::QREG, decltype(SRDV)::value, DROP, QH>);
     };
-    if constexpr (N == 1 && fwd_seq_ok<E, HS, PL::DV, DROP>())
-      if (p.bseq > 1) return go(attn_fwd_kernel<E, HS, N, DVC, NW, FP::QREG, decltype(SRDV)::value, DROP, QH, true>);
-    return go(attn_fwd_kernel<E, HS, N, DVC, NW, FP::QREG, decltype(SRDV)::value, DROP, QH>);
-  };
-  int e = 0;
-  if constexpr (KvRing<E, HS, N, DVC, FwdCfg<E, HS, N, DVC, NW, FP::QREG, QH>::BN, NW>::ok)
-    e = kv_layout_ok(p, (int)sizeof(E)) ? run(std::true_type{}) : run(std::false_type{});
-  else
-    e = run(std::false_type{});
-  if (e) return e;
-  return (int)hipGetLastError();
+    int e = 0;
+    if constexpr (KvRing<E, HS, N, DVC, FwdCfg<E, HS, N, DVC, NW, FP::QREG, QH>::BN, NW>::ok)
+      e = kv_layout_ok(p, (int)sizeof(E)) ? run(std::true_type{}) : run(std::false_type{});
+    else
+      e = run(std::false_type{});
+    if (e) return e;
+    return (int)hipGetLastError();
   }
 }
 
@@ -2878,10 +2604,10 @@ int launch_dkdv_t(const BwdParams& p, hipStream_t st) {
   // accumulators up to 288 of them share one launch (head size 128 at N = 2, cfg5)
   constexpr int HSB = DkdvSplit<HS, N, DV>::HSB;
   constexpr bool FUSED = DkdvSplit<HS, N, DV>::fused ||
-                         (DTA_DKDV_FUSE1 && sizeof(E) == 2 && NW == 4 && !PR && N * HSB / 2 + DV / 2 <= 288);
+                         (sizeof(E) == 2 && NW == 4 && !PR && N * HSB / 2 + DV / 2 <= 288);
   // ABI 8 lse_c (p.lsec): the |c_i|-folded instantiation, built for the 16-bit plans without
   // dropout whose row vectors ride in the ring
-  constexpr bool CAN_FOLD = sizeof(E) == 2 && !DROP && !GR && DTA_DKDV_CFOLD;
+  constexpr bool CAN_FOLD = sizeof(E) == 2 && !DROP && !GR;
   auto run = [&](auto DKV, auto DVVV, auto SRDV) -> int {
     auto launch = [&](auto CFV) -> int {
       auto kern = attn_dkdv_kernel<E, HS, N, DV, NW, decltype(DKV)::value, decltype(DVVV)::value,

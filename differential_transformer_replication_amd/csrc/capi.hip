@@ -338,7 +338,7 @@ int dta_attn_bwd(const dta_attn_bwd_args* a, void* stream) {
   const uint64_t kstarts = rebase ? group_starts(a->dtype, p.HS, p.N, p.DV, kcap) : 0;
   if (stages & DTA_BWD_DQ) {
     // one dQ launch over every branch writes the delta rows straight in the dK/dV encoding
-    const bool direct = DTA_DQ_KSTARTS && qstarts != kstarts && branch_group(a->dtype, p.HS, p.N, p.DV, qcap) == p.N;
+    const bool direct = qstarts != kstarts && branch_group(a->dtype, p.HS, p.N, p.DV, qcap) == p.N;
     for (int g0 = 0, ng; g0 < p.N; g0 += ng) {
       ng = branch_group(a->dtype, p.HS, p.N - g0, p.DV, qcap);
       BwdParams q = group(g0, ng);

@@ -44,15 +44,6 @@ __device__ __forceinline__ float wave_sum_halves(float v) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// XCD-aware workgroup order: blocks are dealt round-robin over the 8 XCDs;
-// remap the linear id so each XCD receives a contiguous range (neighbouring
-// tiles of one (batch, head) then share that XCD's L2).  Bijective for any
-// count (cdna_hip_programming.md T1).  Speed only -- never correctness.
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  const int q = n / 8, r = n % 8, x = id % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + id / 8;
-}
-
 // Dispatch order of the attention grids (grid x = work rank, y / z = head, chunk, batch):
 // the work rank r (0 = the workgroups with the most causal tiles) varies slowest and the
 // (y, z) index fastest.  Blocks are dealt round-robin over the 8 XCDs, so every XCD starts
@@ -60,34 +51,29 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 // long workgroup is left running alone at the end of the grid), and, when gridDim.y *
 // gridDim.z is a multiple of 8, all workgroups of one (y, z) land on one XCD (its L2).
 // Speed only -- never correctness.
-#ifndef DTA_LPT
-#define DTA_LPT 1
-#endif
-// DTA_LPT_GROUP = G > 0 (default 4): each XCD walks its (y, z) pairs G at a time,
+// DTA_LPT_GROUP = G (default 4): each XCD walks its (y, z) pairs G at a time,
 // longest-first inside a group, so only about 2G pairs' K/V (forward, dQ) or Q/dO
 // (dK/dV) are live in that XCD's L2 at once instead of all of them (needs gridDim.y *
-// gridDim.z % 8 == 0; blocks are dealt to XCD id % 8).  One-process A/B at cfg2
+// gridDim.z % 8 == 0; blocks are dealt to XCD id % 8; other grids take the ungrouped
+// longest-first order).  One-process A/B at cfg2
 // (profiles/r03_lpt_group_ab.json): fwd+dq+dkdv 3.052 -> 2.891 ms (G = 1 / 2 / 3 / 6 / 8:
 // 3.140 / 3.001 / 3.081 / 2.926 / 2.912); fabric reads per launch fwd 2575 -> 734 MB,
-// dq 2929 -> 1258, dK/dV 3146 -> 867; cfg3 N=3 1.231 -> 1.211, cfg5 unchanged.  0 = the
-// ungrouped longest-first order.
+// dq 2929 -> 1258, dK/dV 3146 -> 867; cfg3 N=3 1.231 -> 1.211, cfg5 unchanged.
 #ifndef DTA_LPT_GROUP
 #define DTA_LPT_GROUP 4
 #endif
+static_assert(DTA_LPT_GROUP >= 1, "DTA_LPT_GROUP: pairs per group, at least 1");
 // Between 8 and 16 pairs per XCD the walk takes two equal groups instead of groups of
 // DTA_LPT_GROUP (cfg3's 12 pairs: 4 + 4 + 4 -> 6 + 6; one-process A/B profiles/r05zc_ab_lpt_groups.json:
 // cfg3 N = 3 fwd+dq+dkdv 1.099 -> 1.060 ms, N = 4 1.381 -> 1.344; cfg2's 16 pairs keep groups of
 // 4, its 2 x 8 measured equal).
-#ifndef DTA_LPT_HALVES
-#define DTA_LPT_HALVES 1
-#endif
 __device__ __forceinline__ void lpt_order(int& r, int& y, int& z, int& id) {
   id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
   const int nyz = gridDim.y * gridDim.z;
-  if (DTA_LPT && DTA_LPT_GROUP > 0 && nyz % 8 == 0) {
+  if (nyz % 8 == 0) {
     const int xcd = id & 7, s = id >> 3;            // s-th block this XCD receives
     const int per = nyz >> 3, R = gridDim.x;        // pairs per XCD, work ranks
-    const int G = (DTA_LPT_HALVES && per > 8 && per < 16) ? (per + 1) / 2 : DTA_LPT_GROUP;
+    const int G = (per > 8 && per < 16) ? (per + 1) / 2 : DTA_LPT_GROUP;
     const int g = s / (R * G);
     const int gsz = min(G, per - g * G);
     const int t = s - g * R * G;
@@ -97,18 +83,10 @@ __device__ __forceinline__ void lpt_order(int& r, int& y, int& z, int& id) {
     z = pair / gridDim.y;
     return;
   }
-  if (DTA_LPT) {
-    r = id / nyz;
-    const int rest = id - r * nyz;
-    y = rest % gridDim.y;
-    z = rest / gridDim.y;
-  } else {
-    const int lin = xcd_remap(id, gridDim.x * gridDim.y * gridDim.z);
-    r = lin % gridDim.x;
-    y = (lin / gridDim.x) % gridDim.y;
-    z = lin / (gridDim.x * gridDim.y);
-    id = lin;
-  }
+  r = id / nyz;
+  const int rest = id - r * nyz;
+  y = rest % gridDim.y;
+  z = rest / gridDim.y;
 }
 
 template <class E> struct Ops;
@@ -220,17 +198,12 @@ __device__ __forceinline__ void stage_vec(E* dst, const E* src, bool valid) {
 // Store 4 consecutive accumulator values (registers 4g..4g+3) as elements.
 template <class E>
 __device__ __forceinline__ void store4(E* dst, float a, float b, float c, float d) {
-#ifndef DTA_ATTN_NT
-#define DTA_ATTN_NT 0          // 1: the attention epilogues' global stores non-temporal
-#endif
   if constexpr (sizeof(E) == 2) {
     typedef E v4 __attribute__((ext_vector_type(4)));
     v4 v = {(E)a, (E)b, (E)c, (E)d};
-    if constexpr (DTA_ATTN_NT) __builtin_nontemporal_store(v, reinterpret_cast<v4*>(dst));
-    else *reinterpret_cast<v4*>(dst) = v;
+    *reinterpret_cast<v4*>(dst) = v;
   } else {
-    if constexpr (DTA_ATTN_NT) __builtin_nontemporal_store(f32x4{a, b, c, d}, reinterpret_cast<f32x4*>(dst));
-    else *reinterpret_cast<f32x4*>(dst) = f32x4{a, b, c, d};
+    *reinterpret_cast<f32x4*>(dst) = f32x4{a, b, c, d};
   }
 }
 
@@ -246,12 +219,8 @@ __device__ __forceinline__ void load_ob8(const void* base, int64_t off, bool h, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (float)v[j];
   } else {
-#ifndef DTA_OBR_LOAD_NT
-#define DTA_OBR_LOAD_NT 0      // A/B: attn_dq's reads of the fp32 O_i (read once) non-temporal
-#endif
     const f32x4* pa = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + off);
-    const f32x4 a = DTA_OBR_LOAD_NT ? __builtin_nontemporal_load(pa) : *pa;
-    const f32x4 b = DTA_OBR_LOAD_NT ? __builtin_nontemporal_load(pa + 1) : pa[1];
+    const f32x4 a = *pa, b = pa[1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { o[j] = a[j]; o[4 + j] = b[j]; }
   }

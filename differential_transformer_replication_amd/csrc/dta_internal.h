@@ -1,12 +1,8 @@
 // dta_internal.h -- host-side parameter blocks shared between the C-ABI
-// (dta_capi.cpp) and the per-dtype kernel translation units.
+// (capi.hip) and the per-dtype kernel translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#ifndef DTA_DQ_KSTARTS
-#define DTA_DQ_KSTARTS 1   // attn_dq writes the delta rows in the dK/dV grouping's encoding when it holds every branch (no rebase launch)
-#endif
 
 namespace dta {
 
