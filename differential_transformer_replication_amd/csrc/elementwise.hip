@@ -11,8 +11,6 @@
 //  * cast_f32          fp32 dQ accumulator -> activation dtype.
 //  * swiglu / accumulate / swiglu_bias   the training step's fused elementwise passes.
 // Every output is written once with non-temporal stores (DTA_EW_NT).
-#include <type_traits>
-
 #include "dta_common.h"
 #include "dta_internal.h"
 
@@ -836,8 +834,21 @@ __global__ __launch_bounds__(256) void swiglu_bwd_bias_kernel(SwigluParams p, fl
     for (int j = 0; j < 8; ++j) {
       float sg;
       const float sl = silu_f<E>(a[j], sg);
-      db[j] = (float)(E)(d[j] * sl);
-      da[j] = (float)(E)(d[j] * b[j] * (sg * (1.f + a[j] * (1.f - sg))));
+      if constexpr (std::is_same_v<E, _Float16>) {
+        // the products as swiglu_bwd_kernel stores them: rounded to fp32, then to E.  Left to
+        // itself the fp16 build fuses each product with its conversion for the sums
+        // (v_fma_mixlo_f16: one rounding) but not for the packed stores, so dbias was the sum of
+        // values an fp16 ulp off the stored ones wherever double rounding bites.  The empty asm
+        // pins the fp32 products in registers, so both conversions start from them.
+        float pb = d[j] * sl;
+        float pa = d[j] * b[j] * (sg * (1.f + a[j] * (1.f - sg)));
+        asm volatile("" : "+v"(pb), "+v"(pa));
+        db[j] = (float)(E)pb;
+        da[j] = (float)(E)pa;
+      } else {
+        db[j] = (float)(E)(d[j] * sl);
+        da[j] = (float)(E)(d[j] * b[j] * (sg * (1.f + a[j] * (1.f - sg))));
+      }
       sa[j] += da[j];
       sb[j] += db[j];
     }
