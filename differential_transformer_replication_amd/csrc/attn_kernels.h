@@ -31,6 +31,7 @@
 #pragma once
 #include "dta_common.h"
 #include "dta_internal.h"
+#include "layout_checks.h"
 
 #include <type_traits>
 #include <utility>
@@ -624,13 +625,11 @@ struct KvRing {
 };
 
 // K/V descriptors cover [row base, T rows): every branch's K columns inside one
-// row stride, V's DV columns too, extents within the 32-bit record count.
+// row stride, V's DV columns too, extents within the 32-bit record count
+// (layout_checks.h).  Otherwise the tiles are staged by address (SRD = false).
 template <class P>
 inline bool kv_layout_ok(const P& p, int es) {
-  const int64_t ks = p.k.st, vs = p.v.st;
-  if (ks <= 0 || vs <= 0 || p.k.si < 0) return false;
-  if ((int64_t)(p.N - 1) * p.k.si + p.HS > ks || p.DV > vs) return false;
-  return (int64_t)p.T * ks * es < (1ll << 31) && (int64_t)p.T * vs * es < (1ll << 31);
+  return dma_rows_ok(p.T, p.k.st, p.k.si, p.N, p.HS, es) && dma_rows_ok(p.T, p.v.st, 0, 1, p.DV, es);
 }
 
 // Row constants as an extra MFMA k-step (bf16, no dropout): each query row's constants
@@ -1901,12 +1900,8 @@ struct TileRing {
 // columns must lie inside one row stride and the extents must fit the 32-bit
 // record count.  Otherwise the DMA-by-address staging runs.
 inline bool ring_layout_ok(const BwdParams& p, int es) {
-  const int64_t qs = p.q.st, ds = p.dout.st;
-  if (qs <= 0 || ds <= 0 || p.q.si < 0) return false;
-  if ((int64_t)(p.N - 1) * p.q.si + p.HS > qs || p.DV > ds) return false;
-  if ((int64_t)p.T * qs * es >= (1ll << 31) || (int64_t)p.T * ds * es >= (1ll << 31)) return false;
-  if ((int64_t)p.N * p.B * p.H * p.T * 4 >= (1ll << 31)) return false;
-  return true;
+  return dma_rows_ok(p.T, p.q.st, p.q.si, p.N, p.HS, es) && dma_rows_ok(p.T, p.dout.st, 0, 1, p.DV, es) &&
+         dma_rowvecs_ok(p.N, p.B, p.H, p.T);
 }
 
 // --------------------------------------------------- backward: dK, dV ---

@@ -32,6 +32,26 @@
  *   LSE    [i][b][h][t]      fp32, NEGATED log2-sum-exp of the scaled scores (-log2 sum 2^(s*scale*log2e))
  *   coef   [h][i]            fp32, signed branch weights (diff: [1, -lambda];
  *                            N-diff: [+l0, -l1, +l2, ...])
+ *
+ * Strides of a dta_tensor (dta_attn_fwd / dta_attn_bwd; tests/test_gpu_abi_layouts.py):
+ *  - the innermost dimension (d, e) is contiguous: there is no stride for it;
+ *  - ptr and every stride are multiples of 16 bytes (8 elements of a 16-bit dtype, 4 of fp32)
+ *    and no stride is negative; anything else returns DTA_ERR_INVALID before any launch;
+ *  - beyond that each tensor's sb, st, sh, si are free and independent of every other
+ *    tensor's: head-major ([b][h][t]..), row-padded, branch-interleaved ([b][t][i][h][d]) and
+ *    branch-outer ([b][i][t][h][d]) views all compute the same values, and no
+ *    layout is refused.  An input may have a zero stride (one K / V for every batch row,
+ *    sb = 0) or overlapping rows; an output's elements must not overlap;
+ *  - speed: the 16-bit plans with head_size >= 32 stream K_i / V (and, in the key-major
+ *    backward, Q_i / dO) tiles by LDS-DMA through 32-bit buffer descriptors when, for each of
+ *    those tensors, every branch of a row lies inside the row's stride and the rows span less
+ *    than 2 GiB:
+ *        (n_terms - 1) * si + head_size <= st   (V, dO: dv <= st)   and   T * st * sizeof(dtype) < 2^31
+ *    (csrc/layout_checks.h; n_terms: of the launch's branch group).  The packed projection
+ *    layout, head-major and row-padded layouts satisfy it.  Other layouts (branch-outer Q / K,
+ *    rows 2^25 elements apart) run the same kernels with the tiles staged through 64-bit
+ *    addresses: same results -- bitwise, except that bf16 dQ without dropout takes its row
+ *    constants in another rounding order -- at a lower speed.
  */
 #ifndef DIFFATTN_H_
 #define DIFFATTN_H_

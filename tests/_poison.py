@@ -71,6 +71,49 @@ def _carve(nbytes, dtype, shape, strides, device):
     return base, t
 
 
+class Arena:
+    """One poisoned buffer (guard | payload | guard, as ``_carve``) that a test lays strided
+    views out in by hand -- the tensors of a C-ABI call at a layout of the test's choosing.
+
+    ``view()`` hands out a view of the payload and records which payload bytes its elements
+    cover; ``check()`` asserts that every guard byte and every *hole* byte (one no view covers:
+    the pad columns of a padded row, the tail of a buffer) is still 0xFF, so a store that
+    ignores a stride lands in memory the test owns and is reported."""
+
+    def __init__(self, nbytes, device, label="arena"):
+        self.nbytes, self.label = int(nbytes), label
+        self.base = torch.full((GUARD + self.nbytes + GUARD,), FILL, dtype=torch.uint8, device=device)
+        self.covered = torch.zeros(GUARD + self.nbytes + GUARD, dtype=torch.bool, device=device)
+
+    def view(self, dtype, shape, strides, offset=0):
+        """``shape`` / ``strides`` / ``offset`` in elements of ``dtype`` from the payload's start.
+        A zero stride (a broadcast input) is allowed; the view must lie inside the payload."""
+        es = dtype.itemsize
+        shape, strides = tuple(int(n) for n in shape), tuple(int(s) for s in strides)
+        assert offset >= 0 and all(s >= 0 for s in strides) and all(n > 0 for n in shape)
+        reach = offset + sum((n - 1) * s for n, s in zip(shape, strides)) + 1
+        assert reach * es <= self.nbytes, f"{self.label}: view reaches {reach * es} of {self.nbytes} bytes"
+        t = self.base[GUARD:GUARD + self.nbytes].view(dtype).as_strided(shape, strides, GUARD // es + offset)
+        once = tuple(1 if s == 0 else n for n, s in zip(shape, strides))
+        self.covered.as_strided(once + (es,), tuple(s * es for s in strides) + (1,), GUARD + offset * es).fill_(True)
+        return t
+
+    def holes(self):
+        """Number of payload bytes no view covers."""
+        return int((~self.covered[GUARD:GUARD + self.nbytes]).sum())
+
+    def check(self):
+        """Every byte outside the views' elements is still 0xFF (synchronise first)."""
+        bad = (self.base != FILL) & ~self.covered
+        if not bool(bad.any()):
+            return
+        first = int(bad.nonzero()[0]) - GUARD
+        where = ("guard band before the payload" if first < 0 else
+                 "guard band past the payload" if first >= self.nbytes else "hole between the views' elements")
+        raise AssertionError(f"out-of-bounds store: {self.label}: {int(bad.sum())} bytes outside every view written, "
+                             f"first at payload byte offset {first} ({where})")
+
+
 def _assigned_name(frame):
     """The variable the allocation on the frame's current line is assigned to: the target of
     ``x = torch.empty(...)``, or the matching one of ``a, b = torch.empty(..), torch.empty(..)``

@@ -53,3 +53,23 @@ def test_ctypes_structs_match_the_header():
             if got[(cname, f[0])] != off:
                 bad.append((cname, f[0], got[(cname, f[0])], off))
     assert not bad, bad
+
+
+def test_tensor5_takes_any_strides_but_a_strided_innermost_dimension():
+    """dta_tensor has sb, st, sh, si and no stride for d / e: ``tensor5`` passes a view's outer
+    strides through as they are and raises where the innermost dimension is not contiguous."""
+    import torch
+    x = torch.zeros(2, 3, 4, 2, 16)
+    hm = x.permute(0, 2, 1, 3, 4)                        # head-major storage seen as [b][t][h][i][d]
+    t = _lib.tensor5(hm)
+    assert (t.ptr, t.sb, t.st, t.sh, t.si) == (x.data_ptr(), *hm.stride()[:4])
+    v = _lib.tensor5(x[:, :, :, 1])                      # [b][t][h][e]: si unused
+    assert (v.ptr, v.sb, v.st, v.sh, v.si) == (x[:, :, :, 1].data_ptr(), 384, 128, 32, 0)
+    b = _lib.tensor5(x[:1].expand(2, 3, 4, 2, 16))       # a broadcast batch row: sb = 0
+    assert b.sb == 0
+    with pytest.raises(RuntimeError, match="innermost"):
+        _lib.tensor5(x[..., ::2])
+    with pytest.raises(RuntimeError, match="innermost"):
+        _lib.tensor5(x.transpose(-1, -2))
+    with pytest.raises(ValueError):
+        _lib.tensor5(x[0, 0])

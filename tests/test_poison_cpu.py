@@ -226,3 +226,39 @@ def test_unclassified_allocation_is_reported():
         s.verify(RESULTS | {"tmp"}, SCRATCH)
         with pytest.raises(AssertionError, match="result and as scratch"):
             s.verify(RESULTS | {"tmp"}, SCRATCH | {"tmp"})
+
+
+def test_arena_reports_stores_into_holes_and_guards():
+    """``Arena``: hand-laid strided views of one poisoned buffer.  A padded layout's pad columns
+    and the buffer's tail are holes; a store that ignores the row stride lands in one."""
+    rows, cols, pad = 5, 16, 8
+    st = cols + pad
+    a = _poison.Arena(rows * st * 2, "cpu", "padded")
+    v = a.view(torch.bfloat16, (rows, cols), (st, 1))
+    assert a.holes() == rows * pad * 2 and v.isnan().all() and v.data_ptr() % 512 == a.base.data_ptr() % 512
+    v.copy_(torch.ones(rows, cols))
+    a.check()
+    flat = a.base[GUARD:GUARD + a.nbytes].view(torch.bfloat16)
+    flat[cols] = 1.0                                         # the packed position of row 1: a pad column here
+    with pytest.raises(AssertionError, match=r"padded: 2 bytes .*payload byte offset 32 \(hole"):
+        a.check()
+    flat[cols] = v.new_tensor(float("nan")).view(torch.int16).fill_(-1).view(torch.bfloat16)
+    a.check()
+    a.base[GUARD + a.nbytes] = 0
+    with pytest.raises(AssertionError, match="guard band past"):
+        a.check()
+    a.base[GUARD + a.nbytes] = 0xFF
+    a.base[GUARD - 1] = 0
+    with pytest.raises(AssertionError, match="guard band before"):
+        a.check()
+
+
+def test_arena_views_broadcast_overlap_and_bounds():
+    a = _poison.Arena(64 * 4, "cpu")
+    b = a.view(torch.float32, (3, 8), (0, 1), offset=4)      # a zero stride covers its elements once
+    assert b.shape == (3, 8) and a.holes() == (64 - 8) * 4
+    o = a.view(torch.float32, (4, 8), (6, 1), offset=16)     # rows overlapping by two elements (an input)
+    assert a.holes() == (64 - 8 - 26) * 4 and o[0, 6:].data_ptr() == o[1, :2].data_ptr()
+    with pytest.raises(AssertionError, match="view reaches"):
+        a.view(torch.float32, (2, 8), (57, 1))
+    a.check()
