@@ -280,10 +280,13 @@ int dta_attn_bwd(const dta_attn_bwd_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int stages = a->stages ? a->stages : (DTA_BWD_PRE | DTA_BWD_DQ | DTA_BWD_DKDV);
   // (with dcoef_partial the DQ stage's ordered reduce overwrites every dcoef entry: nothing to zero)
-  if ((stages & DTA_BWD_PRE) && !a->dcoef_partial) {
+  const bool empty = (int64_t)a->B * a->T == 0;
+  // no rows: the DQ stage launches nothing, so neither its ordered reduce nor its atomics reach
+  // dcoef; the sum over no rows is zero, written here (a DKDV-only call leaves dcoef alone)
+  if (((stages & DTA_BWD_PRE) && !a->dcoef_partial) || (empty && (stages & DTA_BWD_DQ))) {
     if (hipMemsetAsync(a->dcoef, 0, sizeof(float) * a->H * a->n_terms, st)) return DTA_ERR_LAUNCH;
   }
-  if ((int64_t)a->B * a->T == 0) return DTA_OK;
+  if (empty) return DTA_OK;
   if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->k, a->dtype, true) || !ok_tensor(a->v, a->dtype, false) ||
       !ok_obr(a->obr, a->obr_dtype, a->dtype) || !ok_tensor(a->dout, a->dtype, false) ||
       !ok_tensor(a->dk, a->dtype, true) || !ok_tensor(a->dv_out, a->dtype, false) ||
@@ -370,6 +373,9 @@ static int ln_common(const dta_ln_args* a, bool bwd) {
     return DTA_ERR_UNSUPPORTED;
   const int64_t v = 8;   // kernels move 8 elements per lane access
   if (a->C % v || a->C > 8192) return DTA_ERR_UNSUPPORTED;
+  // no rows: nothing launches (launch_ln), nothing is read or written and dw / db keep what the
+  // caller put there, so an empty tensor's NULL pointers are not an error
+  if (a->rows == 0) return DTA_OK;
   if (!aligned_ptr(a->x) || a->x_stride % v || !a->w || !a->mean || !a->rstd) return DTA_ERR_INVALID;
   if (!bwd && (!aligned_ptr(a->y) || a->y_stride % v || !a->b)) return DTA_ERR_INVALID;
   if (bwd && (!aligned_ptr(a->dy) || !aligned_ptr(a->dx) || a->dy_stride % v || a->dx_stride % v || !a->dw || !a->db))
@@ -429,7 +435,10 @@ int dta_rope(const dta_rope_args* a, void* stream) {
 static int swiglu_common(const dta_swiglu_args* a, bool bwd, SwigluParams& p) {
   if (!a || a->dtype < DTA_BF16 || a->dtype > DTA_F32 || a->rows < 0 || a->n < 0) return DTA_ERR_INVALID;
   if (a->n % 8) return DTA_ERR_UNSUPPORTED;
-  auto ok = [](const void* q, int64_t st) { return aligned_ptr(q) && st % 8 == 0 && st >= 0; };
+  // no elements: nothing launches and no operand is read or written (an empty tensor's pointers
+  // may be NULL); dta_swiglu_bwd still zeroes dbias
+  const bool none = a->rows == 0 || a->n == 0;
+  auto ok = [none](const void* q, int64_t st) { return (none || aligned_ptr(q)) && st % 8 == 0 && st >= 0; };
   if (!ok(a->a, a->a_stride) || !ok(a->b, a->b_stride)) return DTA_ERR_INVALID;
   if (!bwd && !ok(a->out, a->out_stride)) return DTA_ERR_INVALID;
   if (bwd && (!ok(a->dout, a->dout_stride) || !ok(a->da, a->da_stride) || !ok(a->db, a->db_stride)))

@@ -1091,6 +1091,8 @@ def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Te
     if (slots.dtype != torch.int32 or tuple(slots.shape) != (B * Tn,) or not slots.is_contiguous()
             or slots.device != k_new.device or k_pool_u8.device != k_new.device):
         raise RuntimeError(f"slots must be a contiguous device int32 tensor of shape ({B * Tn},) on {k_new.device}")
+    if B * Tn == 0:
+        return                                  # no rows to write (an empty ``slots`` has no address to pass)
     a = _lib.KvQuantRowsArgs(_lib.dtype_code(k_new.dtype), B, Tn, H, N, hs, dv, P, n_all - 1,
                              _lib.tensor5(k_new), _lib.tensor5(v_new), _lib.tensor5(k_pool_u8),
                              _lib.tensor5(v_pool_u8), scale_pool.data_ptr(), scale_pool.stride(0), slots.data_ptr())

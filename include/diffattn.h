@@ -156,7 +156,8 @@ typedef struct dta_attn_bwd_args {
   const float* coef;         /* fp32 [h][i] */
   dta_tensor dout;           /* dO [b][t][h][e] */
   dta_tensor dq, dk, dv_out; /* outputs (dtype) */
-  float* dcoef;              /* output fp32 [h][i] (overwritten) */
+  float* dcoef;              /* output fp32 [h][i] (overwritten; all zero when B * T == 0, written by
+                                the DQ stage, or by PRE without dcoef_partial) */
   float* delta;              /* workspace fp32 [i][b][h][t] */
   float* dq_f32;             /* see above */
   int32_t stages;            /* 0 = all; else bitmask of DTA_BWD_PRE (zero dcoef; a no-op when
@@ -196,7 +197,17 @@ typedef struct dta_attn_bwd_args {
                                 no dropout the DQ stage writes each row's stored LSE_i + log2|c_i| here and
                                 the DKDV stage seeds its scores with it, so its probabilities come out
                                 already scaled by |c_i| (one VALU op per element less in dV's operand).
-                                Requires |c_i| < 2^64.  NULL (or fp32 / dropout): the unfolded kernels. */
+                                When the stages run as separate calls, the DQ and the DKDV call must pass
+                                the SAME lse_c (both the buffer or both NULL): the DKDV stage reads what
+                                the DQ stage wrote there, and with NULL in either it takes the other path.
+                                Range: the kernel packs |c_i| P and |c_i| P (dP - delta_i) to dtype.  bf16
+                                has fp32's exponent range: |c_i| < 2^64.  fp16 overflows at 65504 and its
+                                absolute step below 2^-14 is 2^-24, so |c_i| max|P (dP - delta_i)| must stay
+                                below 65504 and a branch whose |c_i| P (dP - delta_i) lies under ~1e-4
+                                loses bits; 1e-3 <= |c_i| <= 1e3 on unit-variance activations is measured
+                                (profiles/coef_scale_errors.json: every branch's dQ_i / dK_i error equals
+                                the unfolded path's, independent of |c_i|).  Outside that range pass NULL.
+                                NULL (or fp32 / dropout): the unfolded kernels. */
 } dta_attn_bwd_args;
 
 enum { DTA_BWD_PRE = 1, DTA_BWD_DQ = 2, DTA_BWD_DKDV = 4 };
