@@ -33,10 +33,14 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # paged caches (block table over a pool of pages), added the same way
            "dta_attn_decode_paged", "dta_attn_extend_paged",
            # fp8 (e4m3fn) pages with per-(row, head) scales, added the same way
-           "dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
+           "dta_attn_decode_paged_fp8", "dta_kv_quant_rows",
+           # the multi-row step on fp8 pages, added the same way
+           "dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
+# and the later pair of the fp8 extend step (``ops.extend_fp8_supported``)
+FP8_EXTEND_EXPORTS = ("dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
 
 
 class DtaTensor(ctypes.Structure):
@@ -146,6 +150,10 @@ class DecodePagedFp8Args(ctypes.Structure):
     _fields_ = DecodePagedArgs._fields_ + [("scale_pool_dev", ctypes.c_void_p), ("scale_page_stride", ctypes.c_int64)]
 
 
+class ExtendPagedFp8Args(ctypes.Structure):
+    _fields_ = ExtendPagedArgs._fields_ + [("scale_pool_dev", ctypes.c_void_p), ("scale_page_stride", ctypes.c_int64)]
+
+
 class KvQuantRowsArgs(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Tn", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
@@ -210,6 +218,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.dta_attn_decode_paged_fp8.argtypes = [P(DecodePagedFp8Args), ctypes.c_void_p]
             lib.dta_kv_quant_rows.argtypes = [P(KvQuantRowsArgs), ctypes.c_void_p]
             lib.dta_attn_decode_paged_fp8.restype = lib.dta_kv_quant_rows.restype = ctypes.c_int
+        if fp8_extend_symbols(lib):
+            lib.dta_attn_extend_paged_fp8.argtypes = [P(ExtendPagedFp8Args), ctypes.c_void_p]
+            lib.dta_extend_fp8_supported.argtypes = [ctypes.c_int32] * 4
+            lib.dta_attn_extend_paged_fp8.restype = lib.dta_extend_fp8_supported.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -219,6 +231,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
 def fp8_symbols(lib) -> bool:
     """Whether ``lib`` exports the fp8-cache entry points (they arrived inside ABI 9)."""
     return all(hasattr(lib, name) for name in FP8_EXPORTS)
+
+
+def fp8_extend_symbols(lib) -> bool:
+    """Whether ``lib`` exports the fp8 extend entry points (they arrived inside ABI 9, after the
+    fp8-cache ones)."""
+    return all(hasattr(lib, name) for name in FP8_EXTEND_EXPORTS)
 
 
 def check(rc: int) -> None:

@@ -607,17 +607,26 @@ int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int3
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }
 
+int dta_extend_fp8_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
+  return extend_f8_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
+}
+
 // dta_attn_extend and dta_attn_extend_ragged: one validation, one launch path.
+// scales: NULL, or the fp32 scale pool of an fp8 page pool (kc / vc are then byte views)
 extern "C++" template <class A>
 static int extend_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, int pos, const int32_t* pos_dev,
-                       const int32_t* cnt_dev, const PageTable& pg, void* stream) {
+                       const int32_t* cnt_dev, const PageTable& pg, void* stream, const float* scales = nullptr,
+                       int64_t scales_sb = 0) {
   if (!ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
-  if (!extend_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
+  if (scales ? !extend_f8_supported(a->dtype, a->head_size, a->n_terms, a->dv)
+             : !extend_supported(a->dtype, a->head_size, a->n_terms, a->dv))
+    return DTA_ERR_UNSUPPORTED;
   if (pos < 0 || a->t_cap < 0 || (int64_t)pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
   if (a->Tq == 0 || (int64_t)a->B * a->H == 0) return DTA_OK;
   // every operand is read or written by 16-byte vector accesses (O by 8-byte ones)
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(kc, a->dtype, true) ||
-      !ok_tensor(vc, a->dtype, false) || !ok_tensor(a->o, a->dtype, false) || !a->coef)
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef) return DTA_ERR_INVALID;
+  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
+             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
     return DTA_ERR_INVALID;
   ExtendParams p{};
   p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
@@ -625,6 +634,10 @@ static int extend_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, i
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
   p.Tq = a->Tq; p.pos = pos; p.sl2 = a->scale * kLog2e;
   p.pos_dev = pos_dev; p.cnt_dev = cnt_dev; p.cap = a->t_cap;
+  if (scales) {
+    p.kvs = scales; p.kvs_sb = scales_sb;
+    return status(launch_extend_f8(a->dtype, p, (hipStream_t)stream));
+  }
   return status(launch_extend(a->dtype, p, (hipStream_t)stream));
 }
 
@@ -643,6 +656,18 @@ int dta_attn_extend_paged(const dta_attn_extend_paged_args* a, void* stream) {
   if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4 || !page_table(a, pg))
     return DTA_ERR_INVALID;
   return extend_call(a, a->k_pool, a->v_pool, 0, a->pos_dev, a->count_dev, pg, stream);
+}
+
+int dta_attn_extend_paged_fp8(const dta_attn_extend_paged_fp8_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4 || !page_table(a, pg))
+    return DTA_ERR_INVALID;
+  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
+  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
+    return DTA_ERR_INVALID;
+  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  return extend_call(a, a->k_pool, a->v_pool, 0, a->pos_dev, a->count_dev, pg, stream, a->scale_pool_dev,
+                     a->scale_page_stride);
 }
 
 }  // extern "C"

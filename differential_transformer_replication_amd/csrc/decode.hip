@@ -59,9 +59,6 @@ __device__ __forceinline__ void ld8f(const E* p, float* f) {
 // both in phase 2, where a thread owns a key anyway.  A lane reads DTA_F8_KB bytes of a K row
 // and DTA_F8_VB bytes of a V row (8 or 16: the A/B is in DESIGN.md).  Rows >= len_b, their
 // scales included, are never loaded.
-struct f8e4 { uint8_t b; };
-template <class C> inline constexpr bool is_f8 = false;
-template <> inline constexpr bool is_f8<f8e4> = true;
 #ifndef DTA_F8_KB
 #define DTA_F8_KB 16
 #endif

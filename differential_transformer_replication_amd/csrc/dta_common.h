@@ -239,6 +239,12 @@ __device__ __forceinline__ void store4_lds(E* dst, float a, float b, float c, fl
 
 constexpr float LOG2E = 1.4426950408889634f;
 
+// An element of an fp8 page pool: one OCP e4m3fn byte.  The kernels that read a cache take its
+// element type as a template parameter next to the activation type (decode.hip, extend.hip).
+struct f8e4 { uint8_t b; };
+template <class C> inline constexpr bool is_f8 = false;
+template <> inline constexpr bool is_f8<f8e4> = true;
+
 // 32-bit division by a launch constant: q = (umulhi(x, m) + x) >> s, exact for x < 2^31
 // (round-up multiplier; the element index of a launch stays below 2^31 on this path)
 struct FastDiv {

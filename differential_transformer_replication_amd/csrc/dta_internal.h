@@ -164,10 +164,15 @@ struct ExtendParams {
   const int* cnt_dev;  // optional int32 [B]: real rows of sequence b, clamped to [0, Tq]; rows past it are written as zeros
   int cap;             // rows of the cache views (the clamp of pos_dev); paged: max_pages * page size
   PageTable pg;        // paged launch: k / v are the page pool
+  // fp8 cache (dta_attn_extend_paged_fp8; NULL otherwise): as DecodeParams' kvs / kvs_sb
+  const float* kvs;
+  int64_t kvs_sb;
 };
 
 int launch_extend(int dtype, const ExtendParams& p, hipStream_t st);   // extend.hip
 bool extend_supported(int dtype, int hs, int n, int dv);
+int launch_extend_f8(int dtype, const ExtendParams& p, hipStream_t st);   // dtype: q / o; cache rows fp8
+bool extend_f8_supported(int dtype, int hs, int n, int dv);
 int launch_ln(int dtype, const LnParams& p, bool bwd, hipStream_t st);
 int launch_rope(int dtype, bool src_f32, const RopeParams& p, hipStream_t st);
 int launch_dcoef_reduce(const float* part, float* dcoef, int H, int N, int64_t per, hipStream_t st);

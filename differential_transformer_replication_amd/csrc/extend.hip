@@ -41,6 +41,21 @@
 // MFMA would still be NaN), and the per-element mask j <= pos + r uses absolute
 // positions (pos is not tile aligned).  Every lane runs every transposed LDS read
 // (no divergence around them): tiles are padded to 32 rows, never masked by EXEC.
+//
+// fp8 page pools (dta_attn_extend_paged_fp8) are the C = f8e4 instantiations: the cache element
+// type C is a template parameter next to E (the type of q, o and both MFMA operands), as in
+// decode.hip, and with C = E every expression is the one it was.  A lane reads 16 e4m3fn bytes
+// of a row and converts them while it stages the image (v_cvt_pk_f32_fp8):
+//   K_i image  the bare byte values (every e4m3 value is exact in bf16, f16 and f32); the row's
+//              scale k_scale[j][h][i] multiplies the fp32 S^T accumulator, once per (key, branch),
+//              together with scale * log2e: the tile's 32 scales of branch i sit in a per-wave LDS
+//              array next to the images and a lane reads its 16 key rows' as broadcasts
+//   V image    V^ = float(byte) * v_scale[j][h] rounded once to E: the magnitude of the activations
+//              the cache was written from (folded into P instead, an f16 probability times
+//              amax / 448 would underflow); exact in f32
+// Rows at or past the valid length are staged as zeros and their scales are never loaded (0).
+#include <type_traits>
+
 #include "dta_common.h"
 #include "dta_internal.h"
 
@@ -54,17 +69,18 @@ struct ExtendPlan {
   int nw;                // waves per workgroup
   bool qlds;             // Q tile staged in LDS (else operand reads go to global / L1)
   int tiles_off, q_off;  // byte offsets into the dynamic LDS
-  int tile_bytes;        // one wave's K_i + V images
+  int tile_bytes;        // one wave's K_i + V images (fp8 cache: and the tile's 32 K_i scales)
   int bytes;             // total
 };
 
 // LDS: fp32 stats [nw][N][2][32] | fp32 final (m_i, coef_i / l_i) [N][2][32] |
 // nw x (K_i image 32 x (HS + pad), V image 32 x (DV + pad)) | Q images [N][32][HS + pad].
 // The waves' accumulators are reduced through the tile region (32 x DV fp32).
+// f8: the cache rows are fp8; every wave's images are followed by fp32 [32] K_i scales.
 template <class E>
-bool extend_plan(int N, int HS, int DV, ExtendPlan& pl) {
+bool extend_plan(int N, int HS, int DV, ExtendPlan& pl, bool f8 = false) {
   const int es = (int)sizeof(E), pad = Pad<E>::v;
-  pl.tile_bytes = 32 * (HS + pad + DV + pad) * es;
+  pl.tile_bytes = 32 * (HS + pad + DV + pad) * es + (f8 ? 32 * 4 : 0);
   const int qbytes = N * 32 * (HS + pad) * es;
   const int red = 32 * DV * 4;
   for (int nw = 4; nw >= 1; nw >>= 1) {
@@ -103,8 +119,52 @@ __device__ __forceinline__ void stage_rows(E* img, int stride, const E* src, int
   }
 }
 
-template <class E, int NDB, bool QLDS, bool PG>
+// the fp8 pool's version: 16 bytes per lane, converted on the way.  SC: times the row's scale
+// sc[(j0 + r) * sst] (the V image), rounded once to E; else the bare byte values (the K_i image)
+template <class E, bool SC>
+__device__ __forceinline__ void stage_rows_f8(E* img, int stride, const uint8_t* src, int64_t st, int C, int j0,
+                                              int L, int lane, const float* sc, int64_t sst) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const int cpr = C / 16;
+  for (int x = lane; x < 32 * cpr; x += 64) {
+    const int r = x / cpr, c = (x - r * cpr) * 16;
+    const bool ok = j0 + r < L;
+    u32x4 v = u32x4{};
+    float s = 0.f;
+    if (ok) {
+      v = *reinterpret_cast<const u32x4*>(src + (int64_t)(j0 + r) * st + c);
+      if constexpr (SC) s = sc[(int64_t)(j0 + r) * sst];
+    }
+    float f[16];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], false);
+      const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], true);
+      f[4 * w] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
+    }
+    if constexpr (SC) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) f[u] *= s;
+    }
+    E* dst = img + r * stride + c;
+    if constexpr (sizeof(E) == 2) {
+      typename Ops<E>::frag a, b;               // 16-bit images keep 16-byte aligned rows
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { a[u] = (E)f[u]; b[u] = (E)f[8 + u]; }
+      *reinterpret_cast<typename Ops<E>::frag*>(dst) = a;
+      *reinterpret_cast<typename Ops<E>::frag*>(dst + 8) = b;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) dst[u] = f[u];   // odd-stride rows
+    }
+  }
+}
+
+template <class E, int NDB, bool QLDS, bool PG, class C = E>
 __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_off, int q_off, int tile_bytes) {
+  constexpr bool F8 = is_f8<C>;
+  static_assert(!F8 || PG, "the fp8 cache is a paged cache");
+  using KV = std::conditional_t<F8, uint8_t, E>;   // what a cache row holds
   using O = Ops<E>;
   using frag = typename O::frag;
   constexpr int SPB = 32 / O::KSTEP;            // k-steps of one 32-key tile in the PV product
@@ -139,17 +199,36 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   float* fin = reinterpret_cast<float*>(smem) + nw * N * 64;           // [i][m | coef / l][32]
   E* Kw = reinterpret_cast<E*>(smem + tiles_off + wave * tile_bytes);
   E* Vw = Kw + 32 * kstr;
+  [[maybe_unused]] float* Sw = reinterpret_cast<float*>(Vw + 32 * vstr);   // fp8: the staged K_i tile's scales [32]
   E* Qs = reinterpret_cast<E*>(smem + q_off);
 
   const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh;
-  const E* gk = reinterpret_cast<const E*>(p.k.p) + (PG ? 0 : b * p.k.sb) + h * p.k.sh;
-  const E* gv = reinterpret_cast<const E*>(p.v.p) + (PG ? 0 : b * p.v.sb) + h * p.v.sh;
+  const KV* gk = reinterpret_cast<const KV*>(p.k.p) + (PG ? 0 : b * p.k.sb) + h * p.k.sh;
+  const KV* gv = reinterpret_cast<const KV*>(p.v.p) + (PG ? 0 : b * p.v.sb) + h * p.v.sh;
   // paged: key tile kt lies in pool page tile_page(kt) (view base + page * sb); stage_rows then
   // counts rows from jt, the tile's first row inside its page, with the limit L moved along
   [[maybe_unused]] const int pmask = (1 << p.pg.shift) - 1;
   auto tile_page = [&](int kt) -> int64_t {
     if constexpr (PG) return page_of(p.pg, b, kt * 32);
     else return 0;
+  };
+  // one wave stages branch i's K rows / the V rows of a key tile (page pg, rows jt .. jt+31, valid below Lt).
+  // fp8: the scales of (page row r, head h) are kvs[pg][r][h][0 .. N], K_i's at i and V's at N
+  auto stage_k = [&](int64_t pg, int i, int jt, int Lt) {
+    if constexpr (F8) {
+      stage_rows_f8<E, false>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane, nullptr, 0);
+      if (lane < 32)
+        Sw[lane] = jt + lane < Lt ? p.kvs[pg * p.kvs_sb + ((int64_t)(jt + lane) * p.H + h) * (N + 1) + i] : 0.f;
+    } else {
+      stage_rows<E>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane);
+    }
+  };
+  auto stage_v = [&](int64_t pg, int jt, int Lt) {
+    if constexpr (F8)
+      stage_rows_f8<E, true>(Vw, vstr, gv + pg * p.v.sb, p.v.st, DV, jt, Lt, lane,
+                             p.kvs + pg * p.kvs_sb + (int64_t)h * (N + 1) + N, (int64_t)p.H * (N + 1));
+    else
+      stage_rows<E>(Vw, vstr, gv + pg * p.v.sb, p.v.st, DV, jt, Lt, lane);
   };
 
   // rows past the real ones of a partial query tile read the last real row (their result is never stored)
@@ -173,7 +252,9 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
     else return gq + (int64_t)min(r0 + c32, cnt - 1) * p.q.st + i * p.q.si;
   };
   // S^T (keys x queries) of branch i against the staged K_i image, in log2 units;
-  // masked: key kt*32 + rowof(r, hf) above this lane's query position -> -inf
+  // masked: key kt*32 + rowof(r, hf) above this lane's query position -> -inf.
+  // fp8: register r is key row rowof(r, hf), whose scale (0 at and past the valid length, where the
+  // mask holds anyway) rides on scale * log2e
   auto scores = [&](int i, int kt, bool masked) -> f32x16 {
     const E* kr = Kw + c32 * kstr;
     const E* qr = qrow(i);
@@ -181,9 +262,16 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
 #pragma unroll 4
     for (int s = 0; s < nsq; ++s) sa = O::mma(O::row(kr, s, hf), O::row(qr, s, hf), sa);
     const int lim = qlim - kt * 32 - 4 * hf;
+    [[maybe_unused]] f32x4 ks[4];
+    if constexpr (F8) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) ks[g] = *reinterpret_cast<const f32x4*>(Sw + 8 * g + 4 * hf);
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float t = sa[r] * p.sl2;
+      float t;
+      if constexpr (F8) t = sa[r] * (p.sl2 * ks[r >> 2][r & 3]);
+      else t = sa[r] * p.sl2;
       sa[r] = (masked && (r & 3) + 8 * (r >> 2) > lim) ? -INFINITY : t;
     }
     return sa;
@@ -196,7 +284,7 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
     const int jt = PG ? (kt * 32) & pmask : kt * 32, Lt = PG ? L - kt * 32 + jt : L;
     for (int i = 0; i < N; ++i) {
       wave_sync();                                 // the previous image's reads are done
-      stage_rows<E>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane);
+      stage_k(pg, i, jt, Lt);
       wave_sync();
       const f32x16 sa = scores(i, kt, masked);
       float mt = -INFINITY;
@@ -241,11 +329,11 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
     const int64_t pg = tile_page(kt);
     const int jt = PG ? (kt * 32) & pmask : kt * 32, Lt = PG ? L - kt * 32 + jt : L;
     wave_sync();
-    stage_rows<E>(Vw, vstr, gv + pg * p.v.sb, p.v.st, DV, jt, Lt, lane);
+    stage_v(pg, jt, Lt);
     f32x16 pt = {};
     for (int i = 0; i < N; ++i) {
       wave_sync();
-      stage_rows<E>(Kw, kstr, gk + pg * p.k.sb + i * p.k.si, p.k.st, HS, jt, Lt, lane);
+      stage_k(pg, i, jt, Lt);
       wave_sync();
       const f32x16 sa = scores(i, kt, masked);
       const float mi = fin[i * 64 + c32], ci = fin[i * 64 + 32 + c32];
@@ -304,9 +392,9 @@ __global__ __launch_bounds__(256) void extend_kernel(ExtendParams p, int tiles_o
   }
 }
 
-template <class E, int NDB, bool QLDS, bool PG>
+template <class E, int NDB, bool QLDS, bool PG, class C>
 int extend_go(const ExtendParams& p, const ExtendPlan& pl, hipStream_t st) {
-  auto kern = extend_kernel<E, NDB, QLDS, PG>;
+  auto kern = extend_kernel<E, NDB, QLDS, PG, C>;
   // more than the default dynamic LDS limit: raised once per instantiation
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -316,19 +404,19 @@ int extend_go(const ExtendParams& p, const ExtendPlan& pl, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-template <class E, bool PG>
+template <class E, bool PG, class C = E>
 int extend_launch(const ExtendParams& p, hipStream_t st) {
   ExtendPlan pl;
-  if (!extend_plan<E>(p.N, p.HS, p.DV, pl)) return -2;
+  if (!extend_plan<E>(p.N, p.HS, p.DV, pl, is_f8<C>)) return -2;
   const int ndb = p.DV / 32;
   if (pl.qlds) {
-    if (ndb <= 2) return extend_go<E, 2, true, PG>(p, pl, st);
-    if (ndb <= 4) return extend_go<E, 4, true, PG>(p, pl, st);
-    return extend_go<E, 8, true, PG>(p, pl, st);
+    if (ndb <= 2) return extend_go<E, 2, true, PG, C>(p, pl, st);
+    if (ndb <= 4) return extend_go<E, 4, true, PG, C>(p, pl, st);
+    return extend_go<E, 8, true, PG, C>(p, pl, st);
   }
-  if (ndb <= 2) return extend_go<E, 2, false, PG>(p, pl, st);
-  if (ndb <= 4) return extend_go<E, 4, false, PG>(p, pl, st);
-  return extend_go<E, 8, false, PG>(p, pl, st);
+  if (ndb <= 2) return extend_go<E, 2, false, PG, C>(p, pl, st);
+  if (ndb <= 4) return extend_go<E, 4, false, PG, C>(p, pl, st);
+  return extend_go<E, 8, false, PG, C>(p, pl, st);
 }
 
 }  // namespace
@@ -347,6 +435,26 @@ int launch_extend(int dtype, const ExtendParams& p, hipStream_t st) {
     case 0: return p.pg.tbl ? extend_launch<__bf16, true>(p, st) : extend_launch<__bf16, false>(p, st);
     case 1: return p.pg.tbl ? extend_launch<_Float16, true>(p, st) : extend_launch<_Float16, false>(p, st);
     case 2: return p.pg.tbl ? extend_launch<float, true>(p, st) : extend_launch<float, false>(p, st);
+  }
+  return -2;
+}
+
+// q / o in dtype, the cache rows fp8 (e4m3fn) with per-(row, head) scales: paged only.  The shapes
+// both the extend plans and the quantising write (dta_kv_quant_rows) take.
+bool extend_f8_supported(int dtype, int hs, int n, int dv) {
+  if (dtype < 0 || dtype > 2) return false;
+  if (hs < 16 || hs > 128 || hs % 16 || dv < 32 || dv > 256 || dv % 32 || n < 1 || n > 4) return false;
+  ExtendPlan pl;
+  return dtype == 2 ? extend_plan<float>(n, hs, dv, pl, true) : extend_plan<__bf16>(n, hs, dv, pl, true);
+}
+
+int launch_extend_f8(int dtype, const ExtendParams& p, hipStream_t st) {
+  if ((int64_t)p.B * p.H * p.Tq == 0) return 0;
+  if (!p.pg.tbl || !p.kvs || !extend_f8_supported(dtype, p.HS, p.N, p.DV)) return -2;
+  switch (dtype) {
+    case 0: return extend_launch<__bf16, true, f8e4>(p, st);
+    case 1: return extend_launch<_Float16, true, f8e4>(p, st);
+    case 2: return extend_launch<float, true, f8e4>(p, st);
   }
   return -2;
 }

@@ -39,7 +39,8 @@ number of tokens per sequence (``truncate`` rolls the rest back).  ``PagedKVCach
 shared pool of fixed-size pages behind a per-sequence block table, with a host allocator:
 ``release`` hands a finished sequence's pages to the next prompt, ``fork`` shares a prompt's
 pages among its continuations (copy on write); ``kv_dtype="fp8_e4m3"`` stores e4m3fn bytes
-with one fp32 scale per (row, head, K_i | V).  Both run one step (``_seq_model_step``,
+with one fp32 scale per (row, head, K_i | V), and with ``fp8_extend=True`` a multi-row step on
+those pages is one ``ops.diff_attention_extend_paged_fp8`` launch per layer.  Both run one step (``_seq_model_step``,
 ``_seq_attention_step``); the cache says where the new rows go (``write_rows``) and which op
 reads them back (``decode_rows``, ``extend_rows``).
 """
@@ -85,6 +86,7 @@ class KVCache:
         self.graph = None
         self.use_graph = os.environ.get("DTA_DECODE_GRAPH", "1") != "0"
         self.kv_dtype = None                       # rows in the projection's dtype (PagedKVCache may differ)
+        self.fp8_extend = False                    # PagedKVCache: the multi-row step of an fp8 pool is one extend launch
 
     def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
         buf = self.rows.get(layer)
@@ -488,9 +490,10 @@ def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one
         pass
     elif one_row:
         out = cache.decode_rows(kv, q[:, 0], coef, tbl, pos + counts).view(B, 1, H * dv)
-    elif cache.kv_dtype is None and ops.extend_supported(qkv.dtype, hs, N, dv):
+    elif (ops.extend_supported(qkv.dtype, hs, N, dv) if cache.kv_dtype is None
+          else cache.fp8_extend and ops.extend_fp8_supported(qkv.dtype, hs, N, dv)):
         out = cache.extend_rows(kv, q, coef, tbl, pos, counts)
-    else:       # no extend plan for this head size, and no fp8 extend kernel
+    else:       # no extend plan for this shape, or an fp8 pool without ``fp8_extend``
         out = _decode_per_row(lambda i, n: cache.decode_rows(kv, q[:, i], coef, tbl, n), Tn, pos, counts)
     return _attention_tail(attn, out)
 
@@ -752,17 +755,23 @@ class PagedKVCache(KVCache):
 
     KV_DTYPES = (None, "fp8_e4m3")
 
-    def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None):
+    def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None,
+                 fp8_extend: bool = False):
         super().__init__()
         if page_size not in ops.PAGE_SIZES:
             raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
         if kv_dtype not in self.KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r} is not one of {self.KV_DTYPES}")
+        if fp8_extend and kv_dtype is None:
+            raise ValueError("fp8_extend=True needs an fp8 pool (kv_dtype='fp8_e4m3')")
         # "fp8_e4m3": the per-layer pool is uint8 (num_pages + 1, P, W), OCP e4m3fn bytes in the same
         # row layout, next to scale_pool fp32 (num_pages + 1, P, H * (N + 1)): one scale per (row,
         # head, K_i | V).  A step quantises its new rows (ops.kv_quant_rows) and decodes on the bytes
         # (ops.diff_attention_decode_paged_fp8).  None: the pool in the projection's dtype.
+        # fp8_extend: a multi-row step on those bytes is one ops.diff_attention_extend_paged_fp8 launch
+        # where it has a plan; False (the default) keeps one decode launch per row.
         self.kv_dtype = kv_dtype
+        self.fp8_extend = bool(fp8_extend)
         self.scale_pool: Dict[int, torch.Tensor] = {}
         if num_pages < 1:
             raise ValueError("num_pages must be >= 1")
@@ -839,7 +848,9 @@ class PagedKVCache(KVCache):
         return ops.diff_attention_decode_paged_fp8(q, *kv, coef, tbl, lengths)
 
     def extend_rows(self, kv, q, coef, tbl, pos, counts):
-        return ops.diff_attention_extend_paged(q, *kv, coef, tbl, pos, counts)
+        if self.kv_dtype is None:
+            return ops.diff_attention_extend_paged(q, *kv, coef, tbl, pos, counts)
+        return ops.diff_attention_extend_paged_fp8(q, *kv, coef, tbl, pos, counts)
 
     def cache_bytes(self) -> int:
         """Bytes the pools of every layer hold (spare pages included)."""

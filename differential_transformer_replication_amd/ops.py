@@ -757,15 +757,17 @@ def extend_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
 
 
 def _extend(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos: Optional[int] = None,
-            pos_dev: Optional[Tensor] = None, counts: Optional[Tensor] = None, page=None) -> Tensor:
+            pos_dev: Optional[Tensor] = None, counts: Optional[Tensor] = None, page=None,
+            scale_pool: Optional[Tensor] = None) -> Tensor:
     """The tail every extend op ends in, on views its caller has checked: the kernel-plan check
     (no fallback), then the launch.  ``pos``: the host position of ``dta_attn_extend``;
     ``pos_dev`` / ``counts``: the ragged entry point's, with ``page`` = (block_table, P,
-    max_pages, n_pages) the paged one's."""
+    max_pages, n_pages) the paged one's and with ``scale_pool`` the fp8 one's."""
     B, Tq, H, N, hs = q.shape
     dv = v.shape[-1]
-    if not extend_supported(q.dtype, hs, N, dv):
-        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    if not (extend_supported if scale_pool is None else extend_fp8_supported)(q.dtype, hs, N, dv):
+        raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}"
+                           + ("" if scale_pool is None else " on an fp8 pool"))
     coef = coef.detach().to(torch.float32).contiguous()
     o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
     if B * Tq == 0:
@@ -781,8 +783,12 @@ def _extend(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos:
                                         stream)
     else:
         table, P, max_pages, n_pages = page
-        rc = lib.dta_attn_extend_paged(_lib.ExtendPagedArgs(*head, *mid, pos_dev.data_ptr(), _lib.ptr(counts),
-                                                            P, max_pages, n_pages, table.data_ptr()), stream)
+        tail = (pos_dev.data_ptr(), _lib.ptr(counts), P, max_pages, n_pages, table.data_ptr())
+        if scale_pool is None:
+            rc = lib.dta_attn_extend_paged(_lib.ExtendPagedArgs(*head, *mid, *tail), stream)
+        else:
+            rc = lib.dta_attn_extend_paged_fp8(
+                _lib.ExtendPagedFp8Args(*head, *mid, *tail, scale_pool.data_ptr(), scale_pool.stride(0)), stream)
     _lib.check(rc)
     return o.view(B, Tq, H * dv)
 
@@ -1063,6 +1069,53 @@ def diff_attention_decode_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
         raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
     _batch_int32(lengths, B, q, "lengths")
     return _decode(lib, q, k_pool_u8, v_pool_u8, coef, max_length, T_cap, lengths=lengths,
+                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool)
+
+
+def extend_fp8_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
+    """Whether ``diff_attention_extend_paged_fp8`` has a kernel plan for this shape
+    (dta_extend_fp8_supported): what both ``extend_supported`` and ``kv_quant_rows`` take, hs % 16
+    == 0 in 16..128, dv % 32 == 0 up to 256, N <= 4.  False on a library without the entry points."""
+    lib = _lib.load()
+    return _lib.fp8_extend_symbols(lib) and bool(lib.dta_extend_fp8_supported(_lib.dtype_code(dtype), hs, N, dv))
+
+
+def diff_attention_extend_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
+                                    coef: Tensor, block_table: Tensor, pos: Tensor,
+                                    counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_extend_paged`` over an fp8 page pool, one launch: sequence b appends
+    ``counts[b]`` real rows at ``pos[b]`` against its dequantised cache rows 0 ..
+    pos[b]+counts[b]-1 (the new rows' own bytes and scales already written, ``kv_quant_rows``).
+    The kernel converts the bytes while it stages a key tile: q_i times the exact byte values
+    on the MFMA, the fp32 scores times the key's K_i scale, V staged as byte * scale rounded
+    once to q's dtype (exact in fp32).
+
+    q: (B, Tq, H, N, hs) bf16 / f16 / f32 padded (the dtype of the result); pools, scales and
+    ``block_table`` as for ``diff_attention_decode_paged_fp8``; ``pos``, ``counts``, the clamps
+    and the zero rows r >= counts[b] as for ``diff_attention_extend_paged``.  Rows past
+    pos[b]+counts[b] and pages nobody names may hold any bytes and any scales, NaN and Inf
+    included.  Returns (B, Tq, H*dv).  No fallback: raises for a shape without a kernel plan
+    or a library without the entry point (``extend_fp8_supported``)."""
+    lib = _lib.load()
+    if not _lib.fp8_extend_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no fp8 extend entry points (extend_fp8_supported)")
+    _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
+    if q.dim() != 5:
+        raise RuntimeError("q must be (B, Tq, H, N, hs)")
+    B, Tq, H, N, hs = q.shape
+    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
+    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
+        raise RuntimeError("the pool views do not match q")
+    max_pages = _table_pages(block_table, B, q)
+    T_cap = max_pages * P
+    if tuple(coef.shape) != (H, N):
+        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+    _batch_int32(pos, B, q, "pos")
+    if counts is not None:
+        _batch_int32(counts, B, q, "counts")
+    if Tq > T_cap:
+        raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
+    return _extend(lib, q, k_pool_u8, v_pool_u8, coef, T_cap, pos_dev=pos, counts=counts,
                    page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool)
 
 

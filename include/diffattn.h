@@ -547,6 +547,57 @@ typedef struct dta_kv_quant_rows_args {
 } dta_kv_quant_rows_args;
 int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream);
 
+/* The multi-row step on an fp8 pool (still ABI 9; the presence of the two symbols is the
+ * capability check): dta_attn_extend_paged with the cache rows read as e4m3fn bytes and
+ * scales in the format above, one launch for what would otherwise be count_b
+ * dta_attn_decode_paged_fp8 launches per sequence (append to a cached conversation,
+ * verification of draft tokens, scoring; replaces the same reference lines as
+ * dta_attn_extend_paged, diff_transformer.py:57-72 for the newest rows).  For row r of
+ * sequence b
+ *   r <  count_b:  o[b][r][h] = sum_i coef[h][i] * softmax_j(q_i[b][r][h] . K^_i(b, j)[h] * scale, j <= pos_b + r) V^(b, j)[h]
+ *   r >= count_b:  o[b][r][h] = 0
+ * with K^_i(b, j), V^(b, j) the dequantised row j of sequence b (x^ = float(byte) * scale),
+ * never materialised in memory.  dtype is the dtype of q, o and both MFMA operands.
+ * Arithmetic:
+ *   K  the K_i image of a key tile holds the bare byte values (every e4m3 value is exact in
+ *      bf16, f16 and f32); the fp32 accumulator of q_i . byte(K_i[j]) is multiplied by
+ *      k_scale[j][h][i] once per (key, branch), as in dta_attn_decode_paged_fp8
+ *   V  the V image holds V^ = float(byte) * v_scale[j][h] rounded once to the operand type
+ *      (exact in f32).  V's scale is not folded into the probability: P is packed to the
+ *      operand type for the P V product, and an f16 probability times amax / 448 underflows
+ * Everything else is dta_attn_extend_paged's: the two passes, no workspace, only o written,
+ * the clamps of pos_b to [0, t_cap - Tq], of count_b to [0, Tq] and of every page id to
+ * [0, n_pages - 1], the table entries read (p < ceil((pos_b + count_b) / P)), zeros for
+ * rows count_b .. Tq-1, and the exit of a query tile without a real row before any load.
+ * Rows >= pos_b + count_b inside a used page are staged as zeros and their scales are never
+ * loaded; those rows and every page no used entry names may hold any bytes and any scales,
+ * NaN and Inf included.
+ * dta_extend_fp8_supported: 1 for the shapes both dta_extend_supported and
+ * dta_kv_quant_rows take (head_size a multiple of 16 up to 128, dv a multiple of 32 up to
+ * 256, n_terms 1..4, dtype bf16 / f16 / f32), else 0.
+ * Errors: everything dta_attn_extend_paged rejects (the pool views are checked as byte
+ * views), and DTA_ERR_INVALID for a null or not 4-byte aligned scale_pool_dev, a
+ * scale_page_stride below P * H * (N+1), or a byte-pool row or page stride that is not a
+ * multiple of 16; DTA_ERR_UNSUPPORTED where dta_extend_fp8_supported is 0.  Tq == 0 or
+ * B*H == 0: DTA_OK, no launch. */
+typedef struct dta_attn_extend_paged_fp8_args {
+  int32_t dtype;             /* of q and o */
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded) */
+  int32_t t_cap;             /* = max_pages * page_size (>= Tq) */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;   /* k_pool / v_pool: e4m3fn bytes, strides in bytes */
+  const float* coef;         /* fp32 [h][i] */
+  const int32_t* pos_dev;    /* device int32 [B]: absolute position of query row 0 of sequence b */
+  const int32_t* count_dev;  /* device int32 [B] or NULL: real new rows of sequence b */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+  const float* scale_pool_dev;     /* fp32 [page][row < P][h][N+1] */
+  int64_t scale_page_stride;       /* floats from one page's scales to the next */
+} dta_attn_extend_paged_fp8_args;
+int dta_attn_extend_paged_fp8(const dta_attn_extend_paged_fp8_args* a, void* stream);
+int dta_extend_fp8_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every

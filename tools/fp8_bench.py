@@ -17,9 +17,17 @@ pages permuted across the whole pool.
   quality, a seeded DiffTransformer (bf16): cache bytes held per layer in both formats,
   and, teacher-forced on the unquantised run's greedy tokens, the largest |logit
   difference| and the share of equal greedy tokens over 64 decode steps.
+  extend (--extend-only: this leg alone, its own file), Tq in 4, 16, 64, 256 new rows per sequence
+  on top of 512 .. 4096 cached ones, all B sequences at the same length, t_cap 4352:
+    fp8_extend   ops.diff_attention_extend_paged_fp8, one launch
+    fp8_per_row  the per-row loop it replaces (kv_cache._decode_per_row over
+                 ops.diff_attention_decode_paged_fp8: PagedKVCache's default on fp8 pages), Tq launches
+    bf16_extend  ops.diff_attention_extend_paged on a bf16 pool of the same rows
+    The per-row loop costs Tq times a decode step, so a window holds ``inner * 4 // Tq`` (at least 1) calls.
 The fp8 arm is checked against the dequantised rows' bf16-cache result before it is timed.
 Usage: python tools/fp8_bench.py [--out profiles/fp8_bench.json] [--repeats 50] [--warmup 10]
        [--inner 20] [--skip-long] [--skip-quality]
+       python tools/fp8_bench.py --extend-only --out profiles/fp8_extend_bench.json
 -> one JSON line per case (also written to FILE as a JSON list)."""
 import argparse
 import json
@@ -105,6 +113,56 @@ def decode_case(cap, host, repeats, warmup, inner):
     return row
 
 
+EXTEND_CAP = 4096 + 256                       # the longest cached length and the most new rows
+EXTEND_TQ = (4, 16, 64, 256)
+EXTEND_LENGTHS = (512, 1024, 2048, 4096)
+
+
+def extend_cases(repeats, warmup, inner):
+    """One row per (cached length, Tq); the pools are made once."""
+    pool, pool8, scales, table = _pools(EXTEND_CAP, 11)
+    k, v = _views(pool)
+    k8, v8 = _views(pool8)
+    coef = torch.tensor([[1.0, -0.6]] * H, device=DEV)
+    deq = torch.empty_like(pool)                  # the reference for the check: the bf16 kernel on the dequantised rows
+    dk, dv_ = _views(deq)
+    dk.copy_(k8.view(torch.float8_e4m3fn).float() * scales[..., :N, None])
+    dv_.copy_(v8.view(torch.float8_e4m3fn).float() * scales[..., N, None])
+    g = torch.Generator(device=DEV).manual_seed(2)
+    for L in EXTEND_LENGTHS:
+        pos = torch.full((B,), L, dtype=torch.int32, device=DEV)
+        for Tq in EXTEND_TQ:
+            q = torch.randn(B, Tq, H, N, HS, device=DEV, generator=g).to(torch.bfloat16)
+
+            def per_row():
+                return kv_cache._decode_per_row(
+                    lambda i, n: ops.diff_attention_decode_paged_fp8(q[:, i], k8, v8, scales, coef, table, n), Tq, pos,
+                    torch.full_like(pos, Tq))
+
+            got = ops.diff_attention_extend_paged_fp8(q, k8, v8, scales, coef, table, pos).float()
+            want = ops.diff_attention_extend_paged(q, dk, dv_, coef, table, pos).float()
+            rel = ((got - want).abs().max() / want.abs().max()).item()
+            rel_rows = ((got - per_row().float()).abs().max() / want.abs().max()).item()
+            assert rel <= 2e-2 and rel_rows <= 2e-2, (L, Tq, rel, rel_rows)
+            n_in = max(1, inner * 4 // Tq)
+            # bytes the cache rows contribute, per format: every (sequence, head) reads rows 0 .. L + Tq - 1 twice
+            # in the extend kernels (two passes; pass 1 K only) and once per new row in the per-row loop
+            row = {"case": "extend", "page_size": P, "q_dtype": "bf16", "B": B, "H": H, "head_size": HS, "dv": DV,
+                   "n_terms": N, "t_cap": EXTEND_CAP, "cached": L, "Tq": Tq, "repeats": repeats, "warmup": warmup,
+                   "inner": n_in, "fp8_extend_vs_bf16_on_dequantised_rows_rel_err": rel,
+                   "fp8_extend_vs_fp8_per_row_rel_err": rel_rows}
+            arms = {
+                "fp8_extend": lambda: ops.diff_attention_extend_paged_fp8(q, k8, v8, scales, coef, table, pos),
+                "fp8_per_row": per_row,
+                "bf16_extend": lambda: ops.diff_attention_extend_paged(q, k, v, coef, table, pos),
+            }
+            _report(row, interleaved_ms(arms, repeats, warmup, n_in))
+            row["fp8_extend_over_fp8_per_row"] = round(row["fp8_extend_ms"] / row["fp8_per_row_ms"], 4)
+            row["fp8_extend_over_bf16_extend"] = round(row["fp8_extend_ms"] / row["bf16_extend_ms"], 4)
+            row["per_row_wins"] = bool(row["fp8_per_row_ms"] < row["fp8_extend_ms"])
+            yield row
+
+
 def write_case(Bw, Tn, repeats, warmup, inner):
     n_pages = max(Bw * Tn // P, 1) + 3
     g = torch.Generator(device=DEV).manual_seed(7)
@@ -172,12 +230,25 @@ def main():
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--skip-long", action="store_true")
     ap.add_argument("--skip-quality", action="store_true")
+    ap.add_argument("--extend-only", action="store_true", help="the multi-row (extend) leg alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("fp8_bench needs the GPU: there is nothing to time without one")
     if not ops.fp8_cache_supported():
         raise SystemExit("the built library has no fp8-cache entry points")
     r = (args.repeats, args.warmup, args.inner)
+    if args.extend_only:
+        if not ops.extend_fp8_supported(torch.bfloat16, HS, N, DV):
+            raise SystemExit("the built library has no fp8 extend plan for this shape")
+        rows = []
+        for row in extend_cases(*r):
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(rows, fh, indent=1)
+                fh.write("\n")
+        return
     cases = [lambda: decode_case(4096, [512 + (4096 - 512) * b // (B - 1) for b in range(B)], *r)]
     if not args.skip_long:
         cases.append(lambda: decode_case(32768, [32768] * B, *r))
