@@ -102,16 +102,11 @@ int branch_group(int dtype, int hs, int left, int dv, int cap) {
 // dK/dV grouping's encoding: written so by attn_dq when one dQ launch holds every branch
 // (round 6, BwdParams::kstarts, profiles/r06t_ab_dq_kstarts.json), else re-based after the
 // dQ launches (delta_rebase_kernel, ~3-7 us, profiles/r04_bwd_rebase.json).
-// DTA_BWD_GROUP_MAX (A/B builds) overrides both caps.
 int bwd_group_cap(int dtype, int hs, int n, bool dkdv) {
-#ifdef DTA_BWD_GROUP_MAX
-  return DTA_BWD_GROUP_MAX;
-#else
   if (dtype == DTA_F32) return 4;
   if (hs >= 192) return 1;            // head size 256: the single-branch plans (the N = 2 ones spill)
   if (dkdv) return hs >= 64 ? 2 : 4;
   return (hs >= 128 || (hs >= 64 && hs < 96 && n >= 4)) ? 2 : 4;
-#endif
 }
 // group starts of the backward of an N-branch problem as a bit mask (bit i: a group
 // starts at branch i)

@@ -31,19 +31,16 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-#ifndef DTA_DEC_NT
-#define DTA_DEC_NT 0       // 1: the K/V cache stream read with non-temporal loads
-#endif
-template <class E, bool NT = false>
+template <class E>
 __device__ __forceinline__ void ld8f(const E* p, float* f) {
   if constexpr (sizeof(E) == 2) {
     typedef E v8 __attribute__((ext_vector_type(8)));
-    const v8 v = NT ? __builtin_nontemporal_load(reinterpret_cast<const v8*>(p)) : *reinterpret_cast<const v8*>(p);
+    const v8 v = *reinterpret_cast<const v8*>(p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
   } else {
     const f32x4* q = reinterpret_cast<const f32x4*>(p);
-    const f32x4 a = NT ? __builtin_nontemporal_load(q) : q[0], b = NT ? __builtin_nontemporal_load(q + 1) : q[1];
+    const f32x4 a = q[0], b = q[1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { f[j] = a[j]; f[j + 4] = b[j]; }
   }
@@ -56,23 +53,19 @@ __device__ __forceinline__ void ld8f(const E* p, float* f) {
 //   score_ij = (q_i . byte(K_i[j])) * k_scale[j][h][i]     one multiply per (row, branch)
 //   acc_i   += (e_ij * v_scale[j][h]) * byte(V[j])          the row sum l_i keeps e_ij
 // The split kernel asks for the scales of a chunk once, thread = key, before phase 1, and applies
-// both in phase 2, where a thread owns a key anyway.  A lane reads DTA_F8_KB bytes of a K row
-// and DTA_F8_VB bytes of a V row (8 or 16: the A/B is in DESIGN.md).  Rows >= len_b, their
+// both in phase 2, where a thread owns a key anyway.  A lane reads kF8KB bytes of a K row
+// and kF8VB bytes of a V row (8 or 16: the A/B is in DESIGN.md).  Rows >= len_b, their
 // scales included, are never loaded.
-#ifndef DTA_F8_KB
-#define DTA_F8_KB 16
-#endif
-#ifndef DTA_F8_VB
-#define DTA_F8_VB 8        // 16 doubles the V row groups and `part`, and halves the occupancy: slower (A/B)
-#endif
-static_assert((DTA_F8_KB == 8 || DTA_F8_KB == 16) && (DTA_F8_VB == 8 || DTA_F8_VB == 16), "8 or 16 bytes per lane");
+constexpr int kF8KB = 16;
+constexpr int kF8VB = 8;   // 16 doubles the V row groups and `part`, and halves the occupancy: slower (A/B)
+static_assert((kF8KB == 8 || kF8KB == 16) && (kF8VB == 8 || kF8VB == 16), "8 or 16 bytes per lane");
 
 // n (8 or 16) cache elements at p as floats
-template <class C, int n, bool NT = false>
+template <class C, int n>
 __device__ __forceinline__ void ldnf(const C* p, float* f) {
   if constexpr (is_f8<C>) {
     typedef uint32_t uv __attribute__((ext_vector_type(n / 4)));
-    const uv v = NT ? __builtin_nontemporal_load(reinterpret_cast<const uv*>(p)) : *reinterpret_cast<const uv*>(p);
+    const uv v = *reinterpret_cast<const uv*>(p);
 #pragma unroll
     for (int w = 0; w < n / 4; ++w) {
       const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], false);
@@ -81,7 +74,7 @@ __device__ __forceinline__ void ldnf(const C* p, float* f) {
     }
   } else {
     static_assert(n == 8, "16- and 32-bit caches are read 8 elements per lane");
-    ld8f<C, NT>(p, f);
+    ld8f<C>(p, f);
   }
 }
 template <class C>
@@ -233,17 +226,12 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
 // halves the partials (A/B: +4.5% at B=8 H=16 L=32768, slower on smaller grids)
 constexpr int kWideGrid = 8192;
 
-// fp8: 16 bytes per lane of a V row doubles the row groups G and with them `part`; shapes where
-// that would pass 40 KiB of LDS read V 8 bytes per lane
-template <class C, int N, int DV>
-inline constexpr int v_lane_elems = !is_f8<C> ? 8 : (kThreads / (DV / DTA_F8_VB)) * N * (DV + 4) * 4 <= 40960 ? DTA_F8_VB : 8;
-
 template <class E, int N, int HS, int DV, int kChunk, bool PG, class C>
 __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) {
   constexpr bool F8 = is_f8<C>;
   static_assert(!F8 || PG, "the fp8 cache is a paged cache");
-  constexpr int KE = F8 ? DTA_F8_KB : 8;      // K elements per lane
-  constexpr int VE = v_lane_elems<C, N, DV>;  // V elements per lane
+  constexpr int KE = F8 ? kF8KB : 8;          // K elements per lane
+  constexpr int VE = F8 ? kF8VB : 8;          // V elements per lane
   constexpr int LPR = HS / KE;                // lanes per K row
   constexpr int KPW = 64 / LPR;               // keys per wave per load
   constexpr int VPR = DV / VE;                // lanes per V row
@@ -305,7 +293,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         float f[KE];
-        ldnf<C, KE, DTA_DEC_NT>(kp + i * p.k.si, f);
+        ldnf<C, KE>(kp + i * p.k.si, f);
         float d = 0.f;
 #pragma unroll
         for (int u = 0; u < KE; ++u) d = fmaf(q[i][u], f[u], d);
@@ -361,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     for (int u = 0; u < VE; ++u) acc[i][u] = 0.f;
   for (int jj = g; jj < nk; jj += G) {
     float f[VE];
-    ldnf<C, VE, DTA_DEC_NT>(gv + crow(p.v, jj), f);
+    ldnf<C, VE>(gv + crow(p.v, jj), f);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const float e = sc[i][jj];

@@ -10,7 +10,7 @@
 //                      delta_i = <dO, O_i>  (d lambda, SURVEY semantic 5), fixed order.
 //  * cast_f32          fp32 dQ accumulator -> activation dtype.
 //  * swiglu / accumulate / swiglu_bias   the training step's fused elementwise passes.
-// Every output is written once with non-temporal stores (DTA_EW_NT).
+// The row-wise kernels write every activation once, with non-temporal stores (stv).
 #include "dta_common.h"
 #include "dta_internal.h"
 
@@ -20,34 +20,23 @@ template <class E> struct Vec8;
 template <> struct Vec8<__bf16> { typedef bf16x8 t; };
 template <> struct Vec8<_Float16> { typedef f16x8 t; };
 
-// streaming policy of the row-wise kernels' activations (read once, written once):
-// bit 0 = non-temporal loads, bit 1 = non-temporal stores.  One-process A/B at cfg2's
-// GroupLayerNorm and cfg3's RoPE (profiles/r04_ab_ln_nt.json): nt stores 45.6 -> 41.7 us
-// (ln_fwd, 6.44 TB/s), 90.3 -> 76.6 (ln_bwd), 51.3 -> 42.2 (rope, 7.15 TB/s); nt loads
-// slower (52.6 us ln_fwd) with or without them.  Outputs bitwise equal.
-#ifndef DTA_EW_NT
-#define DTA_EW_NT 2
-#endif
+// The row-wise kernels' activations are read once and written once: plain loads,
+// non-temporal stores.  One-process A/B at cfg2's GroupLayerNorm and cfg3's RoPE
+// (profiles/r04_ab_ln_nt.json): nt stores 45.6 -> 41.7 us (ln_fwd, 6.44 TB/s),
+// 90.3 -> 76.6 (ln_bwd), 51.3 -> 42.2 (rope, 7.15 TB/s); nt loads slower (52.6 us ln_fwd)
+// with or without them.  Outputs bitwise equal.
 template <class V>
-__device__ __forceinline__ V ldv(const V* p) {
-  if constexpr (DTA_EW_NT & 1) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-template <class V>
-__device__ __forceinline__ void stv(V* p, V v) {
-  if constexpr (DTA_EW_NT & 2) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
+__device__ __forceinline__ void stv(V* p, V v) { __builtin_nontemporal_store(v, p); }
 
 // load/store 8 consecutive elements as fp32
 template <class E>
 __device__ __forceinline__ void ld8(const E* p, float* f) {
   if constexpr (sizeof(E) == 2) {
-    typename Vec8<E>::t v = ldv(reinterpret_cast<const typename Vec8<E>::t*>(p));
+    typename Vec8<E>::t v = *reinterpret_cast<const typename Vec8<E>::t*>(p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
   } else {
-    f32x4 a = ldv(reinterpret_cast<const f32x4*>(p)), b = ldv(reinterpret_cast<const f32x4*>(p + 4));
+    f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) { f[j] = a[j]; f[j + 4] = b[j]; }
   }
@@ -155,7 +144,7 @@ template <class E> struct Raw8 { typedef s16x8 t; };
 template <> struct Raw8<float> { typedef f32x4 t[2]; };
 
 template <class E>
-__device__ __forceinline__ void raw_ld(const E* p, s16x8& v) { v = ldv(reinterpret_cast<const s16x8*>(p)); }
+__device__ __forceinline__ void raw_ld(const E* p, s16x8& v) { v = *reinterpret_cast<const s16x8*>(p); }
 template <class E>
 __device__ __forceinline__ void raw_cvt(const s16x8& v, float* f) {
   const typename Vec8<E>::t w = __builtin_bit_cast(typename Vec8<E>::t, v);
@@ -266,25 +255,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnParams p) {
   }
 }
 
-// Backward, one workgroup per row at a time (DTA_LN_BWD_ROWBLOCK, default): the four
+// Backward, one workgroup per row at a time (every width the launch below sends here): the four
 // waves split the row's columns (thread t owns 8-column chunks t, t+256, ...), so a
 // thread's dw/db column partials are only 16*CHB registers and need no cross-wave
 // reduction; the row sums (sum g, sum g*xhat) cross waves through a parity-double-
-// buffered LDS slot, one barrier per row.  The x / dy of the rows PD groups ahead are
+// buffered LDS slot, one barrier per row.  The x / dy of the rows PD steps ahead are
 // loaded before the current row's math (a register ring of PD + 1 rows): with 512
 // workgroups (2 per CU, capped so the column partials stay small) one row ahead left
 // ~16 KB in flight per CU; three rows ahead took cfg2's ln_bwd 72.6 -> 68.5 us
 // (profiles/r06o_ab_ln_prefetch_depth.json).  ~114 VGPRs at C = 2048, where the
 // wave-per-row kernel above holds 222.
-#ifndef DTA_LN_BWD_RPI
-#define DTA_LN_BWD_RPI 1         // rows per barrier (each workgroup step)
-#endif
-#ifndef DTA_LN_BWD_PD
-#define DTA_LN_BWD_PD 3          // row groups in flight ahead of the one being computed (1..5)
-#endif
+constexpr int kLnBwdPD = 3;      // rows in flight ahead of the one being computed (1..5)
 // (rows wider than 2048 columns keep one row ahead: they already hold CHB times the bytes in
 // flight per row, and three rows of them cost 206-512 registers, a wave per SIMD or spills)
-template <class E, int CHB, class Y = E, int RPI = DTA_LN_BWD_RPI, int PD = (CHB == 1 ? DTA_LN_BWD_PD : 1)>
+template <class E, int CHB, class Y = E, int PD = (CHB == 1 ? kLnBwdPD : 1)>
 __global__ __launch_bounds__(256) void ln_bwd_rb_kernel(LnParams p) {
   static_assert(PD >= 1 && PD <= 5, "prefetch depth");
   constexpr int NSL = PD + 1;      // register slots of raw rows
@@ -295,43 +279,37 @@ __global__ __launch_bounds__(256) void ln_bwd_rb_kernel(LnParams p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { dwp[c][j] = 0.f; dbp[c][j] = 0.f; }
   const float inv_c = 1.f / (float)p.C;
-  __shared__ float red[2][RPI][4][2];
+  __shared__ float red[2][4][2];
   // raw (unconverted) vectors of 8 elements: one s16x8 for 16-bit, two f32x4 for fp32
   constexpr bool P16 = sizeof(E) == 2, Y16 = sizeof(Y) == 2;
   typedef typename std::conditional<P16, s16x8, f32x4>::type RT;
   typedef typename std::conditional<Y16, s16x8, f32x4>::type RY;
   constexpr int NR = P16 ? 1 : 2, NY = Y16 ? 1 : 2;
-  RT xr[NSL][RPI][CHB][NR];
-  RY dr[NSL][RPI][CHB][NY];
-  float mr[NSL][RPI], rr[NSL][RPI];
+  RT xr[NSL][CHB][NR];
+  RY dr[NSL][CHB][NY];
+  float mr[NSL], rr[NSL];
   const int64_t stride = gridDim.x;
-  // rows r0 + q*stride, q < RPI; past the last row the last row is re-read (masked in the
-  // math): a load behind a branch would leave the wait counters unknown at the join
+  // row r0 into ring slot S.  Every caller checks r0 < rows, so the clamp never binds: it is
+  // what is left of the several-rows-per-barrier layout, kept because the compiler does not
+  // fold it and this kernel's code was to stay bit for bit what it was
   auto load = [&](auto S, int64_t r0) {
     constexpr int s = decltype(S)::value;
+    const int64_t r = min(r0, p.rows - 1);
+    // the row statistics first: a load issued after the next row's prefetch would make
+    // its wait (vmcnt counts in order) drain that prefetch too
+    mr[s] = p.mean[r];
+    rr[s] = p.rstd[r];
+    const E* x = reinterpret_cast<const E*>(p.x) + r * p.xs;
+    const Y* dy = reinterpret_cast<const Y*>(p.dy) + r * p.dys;
+    // unconditional loads (lanes past C read column 0, masked in the math)
 #pragma unroll
-    for (int q = 0; q < RPI; ++q) {
-      const int64_t r = min(r0 + q * stride, p.rows - 1);
-      // the row statistics first: a load issued after the next row's prefetch would make
-      // its wait (vmcnt counts in order) drain that prefetch too
-      mr[s][q] = p.mean[r];
-      rr[s][q] = p.rstd[r];
-    }
+    for (int c = 0; c < CHB; ++c) {
+      const int col0 = (c * 256 + t) * 8;
+      const int col = col0 < p.C ? col0 : 0;
 #pragma unroll
-    for (int q = 0; q < RPI; ++q) {
-      const int64_t r = min(r0 + q * stride, p.rows - 1);
-      const E* x = reinterpret_cast<const E*>(p.x) + r * p.xs;
-      const Y* dy = reinterpret_cast<const Y*>(p.dy) + r * p.dys;
-      // unconditional loads (lanes past C read column 0, masked in the math)
+      for (int k = 0; k < NR; ++k) xr[s][c][k] = *reinterpret_cast<const RT*>(x + col + k * 4);
 #pragma unroll
-      for (int c = 0; c < CHB; ++c) {
-        const int col0 = (c * 256 + t) * 8;
-        const int col = col0 < p.C ? col0 : 0;
-#pragma unroll
-        for (int k = 0; k < NR; ++k) xr[s][q][c][k] = ldv(reinterpret_cast<const RT*>(x + col + k * 4));
-#pragma unroll
-        for (int k = 0; k < NY; ++k) dr[s][q][c][k] = ldv(reinterpret_cast<const RY*>(dy + col + k * 4));
-      }
+      for (int k = 0; k < NY; ++k) dr[s][c][k] = *reinterpret_cast<const RY*>(dy + col + k * 4);
     }
   };
   auto cvt = [&](auto T16, const auto& v, float* f) {
@@ -353,80 +331,70 @@ __global__ __launch_bounds__(256) void ln_bwd_rb_kernel(LnParams p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) wv[c][j] = col < p.C ? p.w[col + j] : 0.f;
   }
-  auto body = [&](auto S, int64_t r0) {
+  auto body = [&](auto S, int64_t r) {
     constexpr int s = decltype(S)::value;
-    if (r0 + PD * RPI * stride < p.rows)                       // the rows PD groups ahead in flight
-      load(std::integral_constant<int, (s + PD) % NSL>{}, r0 + PD * RPI * stride);
-    float xh[RPI][CHB][8], g[RPI][CHB][8];
+    if (r + PD * stride < p.rows)                              // the row PD steps ahead in flight
+      load(std::integral_constant<int, (s + PD) % NSL>{}, r + PD * stride);
+    float xh[CHB][8], g[CHB][8];
+    const float mean = mr[s], rstd = rr[s];
+    float sg = 0.f, sgx = 0.f;
 #pragma unroll
-    for (int q = 0; q < RPI; ++q) {
-      const bool live = r0 + q * stride < p.rows;      // workgroup-uniform
-      const float mean = mr[s][q], rstd = rr[s][q];
-      float sg = 0.f, sgx = 0.f;
+    for (int c = 0; c < CHB; ++c) {
+      const bool ok = (c * 256 + t) * 8 < p.C;
+      float xv[8], dv[8];
+      cvt(E{}, xr[s][c], xv);
+      cvt(Y{}, dr[s][c], dv);
 #pragma unroll
-      for (int c = 0; c < CHB; ++c) {
-        const bool ok = live && (c * 256 + t) * 8 < p.C;
-        float xv[8], dv[8];
-        cvt(E{}, xr[s][q][c], xv);
-        cvt(Y{}, dr[s][q][c], dv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          xh[q][c][j] = ok ? (xv[j] - mean) * rstd : 0.f;
-          const float dys = ok ? dv[j] * p.out_scale : 0.f;
-          dwp[c][j] = fmaf(dys, xh[q][c][j], dwp[c][j]);
-          dbp[c][j] += dys;
-          g[q][c][j] = dys * wv[c][j];
-          sg += g[q][c][j];
-          sgx = fmaf(g[q][c][j], xh[q][c][j], sgx);
-        }
+      for (int j = 0; j < 8; ++j) {
+        xh[c][j] = ok ? (xv[j] - mean) * rstd : 0.f;
+        const float dys = ok ? dv[j] * p.out_scale : 0.f;
+        dwp[c][j] = fmaf(dys, xh[c][j], dwp[c][j]);
+        dbp[c][j] += dys;
+        g[c][j] = dys * wv[c][j];
+        sg += g[c][j];
+        sgx = fmaf(g[c][j], xh[c][j], sgx);
       }
-      sg = wave_sum(sg);
-      sgx = wave_sum(sgx);
-      if (lane == 0) { red[par][q][wave][0] = sg; red[par][q][wave][1] = sgx; }
     }
+    sg = wave_sum(sg);
+    sgx = wave_sum(sgx);
+    if (lane == 0) { red[par][wave][0] = sg; red[par][wave][1] = sgx; }
     // LDS-only barrier: __syncthreads() would also wait for the next rows' prefetch
     __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
+    const float mg = (red[par][0][0] + red[par][1][0] + red[par][2][0] + red[par][3][0]) * inv_c;
+    const float mgx = (red[par][0][1] + red[par][1][1] + red[par][2][1] + red[par][3][1]) * inv_c;
+    E* dx = reinterpret_cast<E*>(p.dx) + r * p.dxs;
 #pragma unroll
-    for (int q = 0; q < RPI; ++q) {
-      const int64_t r = r0 + q * stride;
-      if (r >= p.rows) break;
-      const float rstd = rr[s][q];
-      const float mg = (red[par][q][0][0] + red[par][q][1][0] + red[par][q][2][0] + red[par][q][3][0]) * inv_c;
-      const float mgx = (red[par][q][0][1] + red[par][q][1][1] + red[par][q][2][1] + red[par][q][3][1]) * inv_c;
-      E* dx = reinterpret_cast<E*>(p.dx) + r * p.dxs;
+    for (int c = 0; c < CHB; ++c) {
+      const int col = (c * 256 + t) * 8;
+      if (col < p.C) {
+        float o[8];
 #pragma unroll
-      for (int c = 0; c < CHB; ++c) {
-        const int col = (c * 256 + t) * 8;
-        if (col < p.C) {
-          float o[8];
+        for (int j = 0; j < 8; ++j) o[j] = rstd * (g[c][j] - mg - xh[c][j] * mgx);
+        if constexpr (std::is_same<E, float>::value && Y16) {
+          if (p.dres) {                        // residual fusion: + the residual branch's gradient
+            float d[8];
+            ld8<float>(p.dres + r * p.dress + col, d);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] = rstd * (g[q][c][j] - mg - xh[q][c][j] * mgx);
-          if constexpr (std::is_same<E, float>::value && Y16) {
-            if (p.dres) {                        // residual fusion: + the residual branch's gradient
-              float d[8];
-              ld8<float>(p.dres + r * p.dress + col, d);
-#pragma unroll
-              for (int j = 0; j < 8; ++j) o[j] += d[j];
-            }
-            if (p.dx16) st8<Y>(reinterpret_cast<Y*>(p.dx16) + r * p.dx16s + col, o);
+            for (int j = 0; j < 8; ++j) o[j] += d[j];
           }
-          st8<E>(dx + col, o);
+          if (p.dx16) st8<Y>(reinterpret_cast<Y*>(p.dx16) + r * p.dx16s + col, o);
         }
+        st8<E>(dx + col, o);
       }
     }
     par ^= 1;
   };
   int64_t r = blockIdx.x;
   if (r < p.rows) load(std::integral_constant<int, 0>{}, r);
-  if constexpr (PD >= 2) if (r + RPI * stride < p.rows) load(std::integral_constant<int, 1>{}, r + RPI * stride);
-  if constexpr (PD >= 3) if (r + 2 * RPI * stride < p.rows) load(std::integral_constant<int, 2>{}, r + 2 * RPI * stride);
-  if constexpr (PD >= 4) if (r + 3 * RPI * stride < p.rows) load(std::integral_constant<int, 3>{}, r + 3 * RPI * stride);
-  if constexpr (PD >= 5) if (r + 4 * RPI * stride < p.rows) load(std::integral_constant<int, 4>{}, r + 4 * RPI * stride);
-  // slot s of the ring serves row groups s, s + NSL, ...: the loop unrolled NSL times
+  if constexpr (PD >= 2) if (r + stride < p.rows) load(std::integral_constant<int, 1>{}, r + stride);
+  if constexpr (PD >= 3) if (r + 2 * stride < p.rows) load(std::integral_constant<int, 2>{}, r + 2 * stride);
+  if constexpr (PD >= 4) if (r + 3 * stride < p.rows) load(std::integral_constant<int, 3>{}, r + 3 * stride);
+  if constexpr (PD >= 5) if (r + 4 * stride < p.rows) load(std::integral_constant<int, 4>{}, r + 4 * stride);
+  // slot s of the ring serves rows s, s + NSL, ... of this workgroup: the loop unrolled NSL times
   auto run = [&](auto S) -> bool {
     body(S, r);
-    r += RPI * stride;
+    r += stride;
     return r < p.rows;
   };
   while (r < p.rows) {
@@ -456,41 +424,14 @@ __global__ __launch_bounds__(256) void ln_bwd_rb_kernel(LnParams p) {
   }
 }
 
-// dw / db += the column sums of the per-block partials, in a fixed order: pass 1 sums
-// each of kLnChunks contiguous runs of blocks per column (many threads in flight),
-// pass 2 adds the kLnChunks run sums in order
-constexpr int kLnChunks = 32;
-__global__ __launch_bounds__(256) void ln_bwd_reduce1_kernel(const float* part, int nblk, int64_t C, float* part2) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;      // over 2 * C
-  if (e >= 2 * C) return;
-  const int which = (int)(e / C);
-  const int64_t col = e % C;
-  const int per = (nblk + kLnChunks - 1) / kLnChunks;
-  const int b0 = blockIdx.y * per, b1 = min(nblk, b0 + per);
-  float s = 0.f;
-#pragma unroll 8
-  for (int b = b0; b < b1; ++b) s += part[((int64_t)b * 2 + which) * C + col];
-  part2[(int64_t)blockIdx.y * 2 * C + e] = s;
-}
-__global__ __launch_bounds__(256) void ln_bwd_reduce2_kernel(const float* part2, int64_t C, float* dw, float* db) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= 2 * C) return;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < kLnChunks; ++j) s += part2[(int64_t)j * 2 * C + e];
-  const int64_t col = e % C;
-  (e >= C ? db : dw)[col] += s;
-}
-// The two passes above in ONE launch: a workgroup owns 4*QD consecutive entries of the
-// [2][C] partial row (QD lanes x 4 floats) and one thread row per chunk of blocks
-// (256 / QD chunks), each summing its run of blocks with 16-byte loads; the chunk sums
-// meet in LDS and 4*QD threads add them in chunk order -- a fixed order, so dw / db stay
-// bitwise reproducible (QD = 8: the same order as reduce1 + reduce2, bitwise equal to
-// them).  Saves the second launch, its gap and the part2 round trip (C' is a multiple of
-// 8: quads never straddle dw / db).
-#ifndef DTA_LN_REDUCE_QD
-#define DTA_LN_REDUCE_QD 8
-#endif
+// dw / db += the column sums of the per-block partials, in a fixed order, in one launch: a
+// workgroup owns 4*QD consecutive entries of the [2][C] partial row (QD lanes x 4 floats)
+// and one thread row per chunk of blocks (256 / QD chunks), each summing its run of blocks
+// with 16-byte loads; the chunk sums meet in LDS and 4*QD threads add them in chunk order --
+// a fixed order, so dw / db stay bitwise reproducible.  (C' is a multiple of 8: quads never
+// straddle dw / db.)  QD = 8 keeps the 32 runs of blocks, and so the bits, of the two-launch
+// reduce this replaced, which paid a second launch, its gap and a round trip of the run sums.
+constexpr int kLnReduceQD = 8;
 template <int QD>
 __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* part, int nblk, int64_t C, float* dw, float* db) {
   constexpr int NCH = 256 / QD, W = 4 * QD;
@@ -518,20 +459,10 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* part, i
     }
   }
 }
-#ifndef DTA_LN_REDUCE_ONE
-#define DTA_LN_REDUCE_ONE 1      // the one-launch ordered reduce (0: reduce1 + reduce2)
-#endif
 static void ln_bwd_reduce(const LnParams& p, int nblk, hipStream_t st) {
-  if (DTA_LN_REDUCE_ONE) {
-    constexpr int W = 4 * DTA_LN_REDUCE_QD;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel<DTA_LN_REDUCE_QD>, dim3((unsigned)((2 * p.C + W - 1) / W)), dim3(256), 0, st,
-                       p.partial, nblk, p.C, p.dw, p.db);
-  } else {
-    float* part2 = p.partial + (int64_t)nblk * 2 * p.C;
-    const unsigned g = (unsigned)((2 * p.C + 255) / 256);
-    hipLaunchKernelGGL(ln_bwd_reduce1_kernel, dim3(g, kLnChunks), dim3(256), 0, st, p.partial, nblk, p.C, part2);
-    hipLaunchKernelGGL(ln_bwd_reduce2_kernel, dim3(g), dim3(256), 0, st, part2, p.C, p.dw, p.db);
-  }
+  constexpr int W = 4 * kLnReduceQD;
+  hipLaunchKernelGGL(ln_bwd_reduce_kernel<kLnReduceQD>, dim3((unsigned)((2 * p.C + W - 1) / W)), dim3(256), 0, st,
+                     p.partial, nblk, p.C, p.dw, p.db);
 }
 
 
@@ -588,16 +519,17 @@ static inline int grid_for(int64_t items) {
   return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
 }
 
-#ifndef DTA_LN_BWD_ROWBLOCK
-#define DTA_LN_BWD_ROWBLOCK 1
-#endif
 // blocks of the LN backward: enough waves in flight to cover HBM latency, few enough
 // that the per-block column partials stay small (dta_ln_bwd_workspace_bytes)
-#ifndef DTA_LN_BWD_MAXBLK
-#define DTA_LN_BWD_MAXBLK 512    // workgroups of the backward: occupancy vs partial rows to reduce (1024: +2%, r04_ab_ln_rpi_blocks.json)
-#endif
-int ln_bwd_blocks(int64_t rows) { return (int)std::min<int64_t>((rows + 7) / 8, DTA_LN_BWD_MAXBLK); }
-int64_t ln_bwd_workspace_floats(int64_t rows, int64_t C) { return ((int64_t)ln_bwd_blocks(rows) + kLnChunks) * 2 * C; }
+constexpr int kLnBwdMaxBlk = 512;  // workgroups of the backward: occupancy vs partial rows to reduce (1024: +2%, r04_ab_ln_rpi_blocks.json)
+int ln_bwd_blocks(int64_t rows) { return (int)std::min<int64_t>((rows + 7) / 8, kLnBwdMaxBlk); }
+// ABI (dta_ln_bwd_workspace_bytes): the kernels use the first blocks * 2 * C floats.  The 32
+// further [2][C] rows held the run sums of the retired two-launch reduce; nothing touches
+// them now, but callers size buffers from this figure, so it stays what it was.
+constexpr int kLnWorkspaceSpareRows = 32;
+int64_t ln_bwd_workspace_floats(int64_t rows, int64_t C) {
+  return ((int64_t)ln_bwd_blocks(rows) + kLnWorkspaceSpareRows) * 2 * C;
+}
 
 template <class E>
 int ln_launch(const LnParams& p, bool bwd, hipStream_t st) {
@@ -607,7 +539,7 @@ int ln_launch(const LnParams& p, bool bwd, hipStream_t st) {
 #define DTA_LN(CH_)                                                                    \
   if (ch <= CH_) {                                                                     \
     if (bwd) {                                                                         \
-      if (DTA_LN_BWD_ROWBLOCK && CH_ <= 16 && (CH_ + 3) / 4 * 2048 >= p.C)             \
+      if (CH_ <= 16 && (CH_ + 3) / 4 * 2048 >= p.C)                                    \
         hipLaunchKernelGGL((ln_bwd_rb_kernel<E, (CH_ + 3) / 4>), dim3(bwd_grid), dim3(256), 0, st, p); \
       else                                                                             \
         hipLaunchKernelGGL((ln_bwd_kernel<E, CH_>), dim3(bwd_grid), dim3(256), 0, st, p); \

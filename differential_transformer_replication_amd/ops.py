@@ -437,7 +437,7 @@ def add_layer_norm(x: Tensor, a: Tensor, ln: "LayerNorm"):
     (diff_transformer.py:121-125).  One fused pass when x is the fp32 residual stream
     under autocast and ln emits the autocast dtype; otherwise the two ops."""
     C = x.shape[-1]
-    if (_RES_FUSE and x.is_cuda and x.dtype == torch.float32 and isinstance(ln, LayerNorm) and ln.autocast_out
+    if (x.is_cuda and x.dtype == torch.float32 and isinstance(ln, LayerNorm) and ln.autocast_out
             and torch.is_autocast_enabled("cuda") and ln.weight is not None and ln.bias is not None
             and len(ln.normalized_shape) == 1 and C % 8 == 0 and C <= 8192 and a.shape == x.shape
             and a.dtype in (torch.bfloat16, torch.float16)):
@@ -446,10 +446,6 @@ def add_layer_norm(x: Tensor, a: Tensor, ln: "LayerNorm"):
             return _AddLN.apply(x, a, ln.weight, ln.bias, ln.eps, ln._gpack, ydt)
     xo = x + a
     return xo, ln(xo)
-
-
-_RES_FUSE = os.environ.get("DTA_RES_FUSE", "1") != "0"        # A/B switch: 0 = add, then LayerNorm
-_SWIGLU_BIAS = os.environ.get("DTA_SWIGLU_BIAS", "1") != "0"   # A/B switch: 0 = bias gradient by torch's sum
 
 
 def group_ln_scale(x: Tensor, w: Tensor, b: Tensor, eps: float = 1e-5, out_scale: float = 1.0,
@@ -591,13 +587,11 @@ class _PackedSwiGLU(torch.autograd.Function):
         d2 = dout.to(y2.dtype).contiguous().view(-1, n)
         dy = torch.empty_like(y2)
         # the bias gradient (column sums of dA | dB as stored) comes out of the same pass
-        db = torch.empty(2 * n, device=y2.device, dtype=torch.float32) if _SWIGLU_BIAS else None
+        db = torch.empty(2 * n, device=y2.device, dtype=torch.float32)
         _swiglu_launch(y2, n, None, d2, dy, db)
         with torch.autocast("cuda", enabled=False):
             dx = (dy @ wc).view(*xc.shape[:-1], xc.shape[-1]).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
             dw = packing.weight_grad(dy, xc.reshape(-1, xc.shape[-1]))
-            if db is None:
-                db = dy.sum(0)
         if ctx.holders is not None and all(ctx.needs_input_grad[5:]):
             wh, bh = ctx.holders
             gw = packing._grad_target(wh, ctx.params[:2])

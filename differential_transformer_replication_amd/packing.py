@@ -26,7 +26,6 @@ parameter to the bucket's ready hook itself, instead of autograd running one
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Sequence
 
 import torch
@@ -70,10 +69,6 @@ def bind_grad(holder: Dict, params: Sequence[torch.nn.Parameter], gflat: torch.T
     holder["on_ready"] = on_ready
 
 
-_ACC_KERNEL = os.environ.get("DTA_ACC_KERNEL", "1") != "0"      # A/B switch: 0 = torch's add_
-_SPLITK = os.environ.get("DTA_SPLITK", "1") != "0"              # A/B switch: 0 = one bf16-output GEMM
-
-
 def weight_grad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """dW = dy^T x for token-major (K, O) / (K, I) operands, the weight gradient of a
     Linear over K tokens.  bf16 on the GPU: fp32 output (no bf16 rounding of dW) and,
@@ -83,7 +78,7 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     8192x1024 648 -> 590).  Otherwise the plain GEMM in the operands' dtype."""
     K, O = dy.shape
     I = x.shape[1]
-    if not (_SPLITK and dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16):
+    if not (dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16):
         return dy.t() @ x
     tiles = -(-O // 256) * -(-I // 256)
     S = 8 if tiles <= 16 else (4 if tiles <= 128 else 1)
@@ -101,8 +96,8 @@ def accumulate(g: torch.Tensor, d: torch.Tensor) -> None:
     numel: one HBM-bound HIP launch (dta_accumulate_f32) on the GPU, where torch's
     mixed-dtype add runs at a fraction of the HBM rate."""
     from . import _lib
-    if (_ACC_KERNEL and g.is_cuda and d.is_cuda and g.dtype == torch.float32 and d.dtype in _lib._DTYPES and g.is_contiguous()
-            and d.is_contiguous() and g.numel() == d.numel() and g.data_ptr() % 16 == 0 and d.data_ptr() % 16 == 0):
+    if (g.is_cuda and d.is_cuda and g.dtype == torch.float32 and d.dtype in _lib._DTYPES and g.is_contiguous() and d.is_contiguous()
+            and g.numel() == d.numel() and g.data_ptr() % 16 == 0 and d.data_ptr() % 16 == 0):
         lib = _lib.load()
         _lib.check(lib.dta_accumulate_f32(_lib.dtype_code(d.dtype), g.numel(), d.data_ptr(), g.data_ptr(),
                                           _lib.stream_handle(g.device)))

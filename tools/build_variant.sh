@@ -1,13 +1,18 @@
-# Build lib/libdiffattn_<name>.so: attn_bf16.hip compiled with extra flags (e.g. -DDTA_STAMPS=1),
-# everything else from the regular build.   bash tools/build_variant.sh <name> "<flags>"
+# Build lib/libdiffattn_<name>.so beside the regular library: the csrc Makefile with its own
+# object directory (csrc/build_v/<name>) and the extra flags on the named units (the
+# Makefile's EXTRA_<unit> hook), so the link list is always the Makefile's SRCS.
+#   bash tools/build_variant.sh <name> <unit>[,<unit>...] "<flags>"
+#   bash tools/build_variant.sh stamps attn_bf16 "-DDTA_STAMPS=1"
+#   bash tools/build_variant.sh c512 capi,decode "-DDTA_DECODE_CHUNK=512"
+# Load the result with DTA_LIB=<path> or as name=lib/libdiffattn_<name>.so (tools/ab_kernels.py).
 set -e
-NAME=$1; EXTRA=$2
+NAME=$1; UNITS=$2; EXTRA=$3
+[ -n "$NAME" ] && [ -n "$UNITS" ] || { echo "usage: $0 <name> <unit>[,<unit>...] \"<flags>\"" >&2; exit 2; }
 C=$(dirname $0)/../differential_transformer_replication_amd/csrc
-make -C $C -j8 >/dev/null
-FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -munsafe-fp-atomics -fno-honor-nans -fno-slp-vectorize -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-but-set-variable"
-mkdir -p $C/build_v
-/opt/rocm/bin/hipcc $FLAGS $EXTRA -c ${SRC:-$C/attn_bf16.hip} -o $C/build_v/attn_bf16_$NAME.o
-/opt/rocm/bin/hipcc $FLAGS $EXTRA -c $C/capi.hip -o $C/build_v/capi_$NAME.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $C/build_v/capi_$NAME.o $C/build/elementwise.o $C/build/decode.o \
-  $C/build/attn_f16.o $C/build/attn_f32.o $C/build/attn_bf16_drop.o $C/build/attn_f16_drop.o $C/build/attn_f32_drop.o $C/build_v/attn_bf16_$NAME.o -o $C/../lib/libdiffattn_$NAME.so
+ARGS=()
+for u in ${UNITS//,/ }; do
+  [ -f $C/$u.hip ] || { echo "no unit $u.hip in $C" >&2; exit 2; }
+  ARGS+=("EXTRA_$u=$EXTRA")
+done
+make -C $C -j${JOBS:-8} BUILD=build_v/$NAME OUT=../lib/libdiffattn_$NAME.so "${ARGS[@]}"
 echo built lib/libdiffattn_$NAME.so

@@ -1,5 +1,5 @@
 """Cycle shares of the forward and dK/dV tile loops from a DTA_STAMPS=1 build
-(tools/build_variant.sh stamps "-DDTA_STAMPS=1").  Read the SHARES, not the
+(tools/build_variant.sh stamps attn_bf16 "-DDTA_STAMPS=1").  Read the SHARES, not the
 length: the stamps' lgkmcnt(0) waits serialise LDS reads.
 
     python tools/stamps.py lib/libdiffattn_stamps.so [--shape B,H,hs,N,T]
