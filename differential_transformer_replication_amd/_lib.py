@@ -35,12 +35,18 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # fp8 (e4m3fn) pages with per-(row, head) scales, added the same way
            "dta_attn_decode_paged_fp8", "dta_kv_quant_rows",
            # the multi-row step on fp8 pages, added the same way
-           "dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
+           "dta_attn_extend_paged_fp8", "dta_extend_fp8_supported",
+           # the split-key decode for a step of 2 .. 8 rows, added the same way
+           "dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
+           "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
 # and the later pair of the fp8 extend step (``ops.extend_fp8_supported``)
 FP8_EXTEND_EXPORTS = ("dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
+# and the split-key decode for a step of 2 .. 8 rows (``ops.decode_rows_supported``), added the same way
+ROWS_EXPORTS = ("dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
+                "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
 
 
 class DtaTensor(ctypes.Structure):
@@ -154,6 +160,20 @@ class ExtendPagedFp8Args(ctypes.Structure):
     _fields_ = ExtendPagedArgs._fields_ + [("scale_pool_dev", ctypes.c_void_p), ("scale_page_stride", ctypes.c_int64)]
 
 
+class DecodeRowsArgs(ctypes.Structure):
+    _fields_ = _cache_op_fields(("Tq", "t_cap"), "k_cache", "v_cache", ("workspace", "pos_dev", "count_dev"))
+
+
+class DecodeRowsPagedArgs(ctypes.Structure):
+    _fields_ = (_cache_op_fields(("Tq", "t_cap"), "k_pool", "v_pool", ("workspace", "pos_dev", "count_dev"))
+                + _PAGED_FIELDS)
+
+
+class DecodeRowsPagedFp8Args(ctypes.Structure):
+    _fields_ = DecodeRowsPagedArgs._fields_ + [("scale_pool_dev", ctypes.c_void_p),
+                                               ("scale_page_stride", ctypes.c_int64)]
+
+
 class KvQuantRowsArgs(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Tn", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
@@ -222,6 +242,16 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.dta_attn_extend_paged_fp8.argtypes = [P(ExtendPagedFp8Args), ctypes.c_void_p]
             lib.dta_extend_fp8_supported.argtypes = [ctypes.c_int32] * 4
             lib.dta_attn_extend_paged_fp8.restype = lib.dta_extend_fp8_supported.restype = ctypes.c_int
+        if rows_symbols(lib):
+            lib.dta_attn_decode_rows.argtypes = [P(DecodeRowsArgs), ctypes.c_void_p]
+            lib.dta_attn_decode_rows_paged.argtypes = [P(DecodeRowsPagedArgs), ctypes.c_void_p]
+            lib.dta_attn_decode_rows_paged_fp8.argtypes = [P(DecodeRowsPagedFp8Args), ctypes.c_void_p]
+            lib.dta_attn_decode_rows_workspace_bytes.argtypes = [ctypes.c_int32] * 7
+            lib.dta_attn_decode_rows_workspace_bytes.restype = ctypes.c_size_t
+            lib.dta_decode_rows_supported.argtypes = [ctypes.c_int32] * 6
+            for fn in ROWS_EXPORTS:
+                if fn != "dta_attn_decode_rows_workspace_bytes":
+                    getattr(lib, fn).restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -237,6 +267,12 @@ def fp8_extend_symbols(lib) -> bool:
     """Whether ``lib`` exports the fp8 extend entry points (they arrived inside ABI 9, after the
     fp8-cache ones)."""
     return all(hasattr(lib, name) for name in FP8_EXTEND_EXPORTS)
+
+
+def rows_symbols(lib) -> bool:
+    """Whether ``lib`` exports the multi-row split-key decode entry points (they arrived inside
+    ABI 9, after the fp8 extend ones)."""
+    return all(hasattr(lib, name) for name in ROWS_EXPORTS)
 
 
 def check(rc: int) -> None:

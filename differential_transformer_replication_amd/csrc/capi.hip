@@ -576,6 +576,72 @@ int dta_attn_decode_paged_fp8(const dta_attn_decode_paged_fp8_args* a, void* str
   return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, a->scale_pool_dev, a->scale_page_stride);
 }
 
+// ---- split-key decode for a step of 1 .. 8 rows per sequence -----------------------------------
+int dta_decode_rows_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t Tq,
+                              int32_t fp8_cache) {
+  (void)fp8_cache;   // every plan is built for 16-bit, 32-bit and e4m3 caches alike
+  return decode_rows_supported(dtype, head_size, n_terms, dv, Tq) ? 1 : 0;
+}
+
+size_t dta_attn_decode_rows_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, int32_t head_size, int32_t dv,
+                                            int32_t t_cap, int32_t Tq) {
+  (void)head_size;
+  if (B < 0 || H < 0 || n_terms < 0 || dv < 0 || t_cap < 0 || Tq < 0) return 0;
+  return (size_t)B * H * Tq * decode_splits(t_cap) * n_terms * (dv + 2) * 4;
+}
+
+// dta_attn_decode_rows, _paged and _paged_fp8: one validation, one launch path (decode_call's
+// checks of the operands, extend_call's of the step)
+extern "C++" template <class A>
+static int decode_rows_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const PageTable& pg, void* stream,
+                            const float* scales = nullptr, int64_t scales_sb = 0) {
+  if (!a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  if (a->Tq < 1 || a->Tq > 8) return DTA_ERR_INVALID;
+  if (!ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (!decode_rows_supported(a->dtype, a->head_size, a->n_terms, a->dv, a->Tq)) return DTA_ERR_UNSUPPORTED;
+  if (a->t_cap < a->Tq) return DTA_ERR_INVALID;
+  if ((int64_t)a->B * a->H == 0) return DTA_OK;
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
+    return DTA_ERR_INVALID;
+  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
+             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
+    return DTA_ERR_INVALID;
+  DecodeParams p{};
+  p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
+  p.coef = a->coef; p.ws = a->workspace;
+  p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
+  p.L = a->t_cap; p.ldw = a->t_cap; p.scale = a->scale;
+  p.Tq = a->Tq; p.pos_dev = a->pos_dev; p.cnt_dev = a->count_dev;
+  p.S = (int)decode_splits(a->t_cap);
+  p.ml = a->workspace + (int64_t)a->B * a->H * a->Tq * p.S * a->n_terms * a->dv;   // after the partial rows
+  if (scales) {
+    p.kvs = scales; p.kvs_sb = scales_sb;
+    return status(launch_decode_rows_f8(a->dtype, p, (hipStream_t)stream));
+  }
+  return status(launch_decode_rows(a->dtype, p, (hipStream_t)stream));
+}
+
+int dta_attn_decode_rows(const dta_attn_decode_rows_args* a, void* stream) {
+  if (!a) return DTA_ERR_INVALID;
+  return decode_rows_call(a, a->k_cache, a->v_cache, PageTable{}, stream);
+}
+
+int dta_attn_decode_rows_paged(const dta_attn_decode_rows_paged_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !page_table(a, pg)) return DTA_ERR_INVALID;
+  return decode_rows_call(a, a->k_pool, a->v_pool, pg, stream);
+}
+
+int dta_attn_decode_rows_paged_fp8(const dta_attn_decode_rows_paged_fp8_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !page_table(a, pg)) return DTA_ERR_INVALID;
+  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
+  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
+    return DTA_ERR_INVALID;
+  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  return decode_rows_call(a, a->k_pool, a->v_pool, pg, stream, a->scale_pool_dev, a->scale_page_stride);
+}
+
 int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream) {
   if (!a || !ok_dims(a->dtype, a->B, a->Tn, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (a->head_size % 16 || a->dv % 16 || a->head_size > 128 || a->dv > 256 || a->n_terms > 4)

@@ -1,4 +1,4 @@
-// decode.hip -- one-query-row differential attention over a KV cache, gfx950.
+// decode.hip -- one-query-row (and, split-key plan, up to eight-row) differential attention over a KV cache, gfx950.
 //
 // The reference's generate() (diff_transformer.py:177-185, Ndiff_transformer.py
 // generate, control.py:163-171) re-runs the whole prefix for every new token.
@@ -226,9 +226,39 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DecodeParams p) {
 // halves the partials (A/B: +4.5% at B=8 H=16 L=32768, slower on smaller grids)
 constexpr int kWideGrid = 8192;
 
-template <class E, int N, int HS, int DV, int kChunk, bool PG, class C>
+// ---- several query rows per launch (dta_attn_decode_rows*) --------------------------
+// R > 1 instantiates the same two kernels for a step of Tq <= kMaxRows new rows per sequence:
+// query row r of sequence b sits at pos_b + r and is the one-row decode at length pos_b + r + 1.
+// A workgroup loads every K and V row of its chunk once (rows < pos_b + count_b only) and
+// carries R rows through the three phases at a time: R query vectors and R accumulators per
+// lane, R * N score rows in LDS.  Where R < count_b the rows go in passes of R (the later
+// passes find the chunk in cache).  Row r masks the keys >= its own length exactly where the
+// one-row kernel masks the keys >= L (score -inf, probability 0), so its max, its sums and
+// its accumulators see the same operands in the same order; the keys between its length and
+// the step's end enter its accumulators as fmaf(0, v, acc) with v a real row of this step.
+// `part` is reused row by row for the cross-group sum and shares its LDS with the scores,
+// which are dead by then.  With R = 1 every expression below is the one-row kernel's.
+constexpr int kMaxRows = 8;
+// rows per pass: the most (of 8, 4, 2) whose query vectors and accumulators stay in registers
+template <int N, class C>
+constexpr int rows_per_pass() {
+  constexpr int per = N * (is_f8<C> ? (kF8KB > kF8VB ? kF8KB : kF8VB) : 8);
+  return per * 8 <= 128 ? 8 : per * 4 <= 128 ? 4 : 2;
+}
+// sequence b's step: position of query row 0 and number of real rows, clamped so that no
+// device value can index past the cache, the workspace or LDS (the extend kernels' clamps)
+struct RowSpan { int pos, cnt; };
+__device__ __forceinline__ RowSpan row_span(const DecodeParams& p, int b) {
+  RowSpan r;
+  r.pos = min(max(p.pos_dev[b], 0), p.ldw - p.Tq);
+  r.cnt = p.cnt_dev ? min(max(p.cnt_dev[b], 0), p.Tq) : p.Tq;
+  return r;
+}
+
+template <class E, int N, int HS, int DV, int kChunk, bool PG, class C, int R>
 __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) {
   constexpr bool F8 = is_f8<C>;
+  constexpr bool ROWS = R > 1;
   static_assert(!F8 || PG, "the fp8 cache is a paged cache");
   constexpr int KE = F8 ? kF8KB : 8;          // K elements per lane
   constexpr int VE = F8 ? kF8VB : 8;          // V elements per lane
@@ -238,13 +268,24 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   constexpr int G = kThreads / VPR;           // V row groups
   constexpr int KPT = kChunk / kThreads;      // keys per thread in the softmax phase
   static_assert(kChunk % kThreads == 0, "chunk must be a multiple of the workgroup");
-  __shared__ float sc[N][kChunk];
-  __shared__ float red[kWaves * N];
-  __shared__ float part[G][N][DV + 4];
+  constexpr int kSc = R * N * kChunk, kPart = G * N * (DV + 4);
+  __shared__ float lds[ROWS ? (kSc > kPart ? kSc : kPart) : kSc + kPart];
+  float (*sc)[N][kChunk] = reinterpret_cast<float (*)[N][kChunk]>(lds);                        // [R][N][kChunk]
+  float (*part)[N][DV + 4] = reinterpret_cast<float (*)[N][DV + 4]>(lds + (ROWS ? 0 : kSc));   // [G][N][DV + 4]
+  __shared__ float red[kWaves * N * R];
   __shared__ int pgs[PG ? kChunk / 32 : 1];   // paged: the chunk's pool pages (page size >= 32)
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j0 = s * kChunk, L = clamp_len(p, b);
+  const int j0 = s * kChunk;
+  // L: the keys the workgroup may load (rows: up to the step's last real row; none without one)
+  int pos = 0, cnt = 1, L;
+  if constexpr (ROWS) {
+    const RowSpan sp = row_span(p, b);
+    pos = sp.pos; cnt = sp.cnt;
+    L = cnt ? pos + cnt : 0;
+  } else {
+    L = clamp_len(p, b);
+  }
   if (j0 >= L) return;                         // grid sized for an upper bound; a chunk past its own
                                                // sequence's length touches no memory (uniform exit)
   const int nk = min(kChunk, L - j0);
@@ -274,118 +315,193 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     }
   }
 
+  // rows: passes of R rows (one pass, cnt = 1, for the one-row kernel)
+  for (int r0 = 0; r0 < cnt; r0 += R) {
+  const int nr = ROWS ? min(R, cnt - r0) : 1;   // real rows of this pass
+  // nkr[x]: the keys of this chunk that row x attends to (0: the chunk lies past the row, or no row)
+  int nkr[R];
+#pragma unroll
+  for (int x = 0; x < R; ++x)
+    nkr[x] = ROWS ? (x < nr ? min(max(pos + r0 + x + 1 - j0, 0), nk) : 0) : nk;
+  if constexpr (ROWS) {
+    if (pos + r0 + nr <= j0) continue;          // the chunk lies past every row of the pass (uniform)
+  }
+
   // phase 1: scores of this chunk into LDS
   {
     const int sub = lane % LPR, kr = lane / LPR;
     const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh + sub * KE;
-    float q[N][KE];
+    float q[R][N][KE];
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
+    for (int x = 0; x < R; ++x) {
 #pragma unroll
-      for (int c = 0; c < KE; c += 8) ld8f<E>(gq + i * p.q.si + c, q[i] + c);
+      for (int i = 0; i < N; ++i) {
+        if (x < nr) {
+          const E* gx = ROWS ? gq + (int64_t)(r0 + x) * p.q.st : gq;
 #pragma unroll
-      for (int u = 0; u < KE; ++u) q[i][u] *= p.scale;
+          for (int c = 0; c < KE; c += 8) ld8f<E>(gx + i * p.q.si + c, q[x][i] + c);
+#pragma unroll
+          for (int u = 0; u < KE; ++u) q[x][i][u] *= p.scale;
+        } else {
+#pragma unroll
+          for (int u = 0; u < KE; ++u) q[x][i][u] = 0.f;
+        }
+      }
     }
     const C* gk = reinterpret_cast<const C*>(p.k.p) + h * p.k.sh + sub * KE;
     for (int jj = wave * KPW + kr; jj < kChunk; jj += kWaves * KPW) {
       const bool ok = jj < nk;
       const C* kp = gk + crow(p.k, ok ? jj : 0);
+      float f[N][KE];
 #pragma unroll
-      for (int i = 0; i < N; ++i) {
-        float f[KE];
-        ldnf<C, KE>(kp + i * p.k.si, f);
-        float d = 0.f;
+      for (int i = 0; i < N; ++i) ldnf<C, KE>(kp + i * p.k.si, f[i]);
 #pragma unroll
-        for (int u = 0; u < KE; ++u) d = fmaf(q[i][u], f[u], d);
+      for (int x = 0; x < R; ++x) {
+        if (x < nr) {
 #pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-        if (sub == 0) sc[i][jj] = ok ? d : -INFINITY;
+          for (int i = 0; i < N; ++i) {
+            float d = 0.f;
+#pragma unroll
+            for (int u = 0; u < KE; ++u) d = fmaf(q[x][i][u], f[i][u], d);
+#pragma unroll
+            for (int o = LPR / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+            if (sub == 0) sc[x][i][jj] = jj < nkr[x] ? d : -INFINITY;
+          }
+        }
       }
     }
   }
   __syncthreads();
 
-  // phase 2: chunk max / exp / sum per branch (thread = key)
-  float m[N], l[N];
+  // phase 2: chunk max / exp / sum per (row, branch) (thread = key)
+  float m[R * N], l[R * N];
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    if constexpr (F8) {
-      // the row's K_i scale: once per (row, branch); rows >= nk keep their -inf
-      m[i] = -INFINITY;
+  for (int x = 0; x < R; ++x) {
 #pragma unroll
-      for (int r = 0; r < KPT; ++r) {
-        const int j = tid + r * kThreads;
-        if (j < nk) sc[i][j] *= ksc[r][i];
-        m[i] = fmaxf(m[i], sc[i][j]);
+    for (int i = 0; i < N; ++i) {
+      float& mi = m[x * N + i];
+      if (x >= nr) {
+        mi = -INFINITY;
+      } else if constexpr (F8) {
+        // the row's K_i scale: once per (row, branch); rows >= nkr keep their -inf
+        mi = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+          const int j = tid + r * kThreads;
+          if (j < nkr[x]) sc[x][i][j] *= ksc[r][i];
+          mi = fmaxf(mi, sc[x][i][j]);
+        }
+      } else {
+        mi = sc[x][i][tid];
+#pragma unroll
+        for (int r = 1; r < KPT; ++r) mi = fmaxf(mi, sc[x][i][tid + r * kThreads]);
       }
-    } else {
-      m[i] = sc[i][tid];
-#pragma unroll
-      for (int r = 1; r < KPT; ++r) m[i] = fmaxf(m[i], sc[i][tid + r * kThreads]);
     }
   }
-  block_reduce<N, true>(m, red);
+  block_reduce<R * N, true>(m, red);
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    l[i] = 0.f;
+  for (int x = 0; x < R; ++x) {
 #pragma unroll
-    for (int r = 0; r < KPT; ++r) {
-      const int j = tid + r * kThreads;
-      const float e = j < nk ? __expf(sc[i][j] - m[i]) : 0.f;
-      if constexpr (F8) sc[i][j] = e * ksc[r][N];      // V's scale rides on the probability; l_i does not see it
-      else sc[i][j] = e;
-      l[i] += e;
+    for (int i = 0; i < N; ++i) {
+      float& li = l[x * N + i];
+      li = 0.f;
+      if (x < nr) {
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+          const int j = tid + r * kThreads;
+          const float e = j < nkr[x] ? __expf(sc[x][i][j] - m[x * N + i]) : 0.f;
+          if constexpr (F8) sc[x][i][j] = e * ksc[r][N];   // V's scale rides on the probability; l_i does not see it
+          else sc[x][i][j] = e;
+          li += e;
+        }
+      }
     }
   }
-  block_reduce<N, false>(l, red);        // its barriers also publish sc
+  block_reduce<R * N, false>(l, red);    // its barriers also publish sc
 
   // phase 3: acc_i = sum_j e_ij V_j (thread = VE columns of one row group)
   const int g = tid / VPR, c0 = (tid % VPR) * VE;
   const C* gv = reinterpret_cast<const C*>(p.v.p) + h * p.v.sh + c0;
-  float acc[N][VE];
+  float acc[R][N][VE];
 #pragma unroll
-  for (int i = 0; i < N; ++i)
+  for (int x = 0; x < R; ++x)
 #pragma unroll
-    for (int u = 0; u < VE; ++u) acc[i][u] = 0.f;
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int u = 0; u < VE; ++u) acc[x][i][u] = 0.f;
   for (int jj = g; jj < nk; jj += G) {
     float f[VE];
     ldnf<C, VE>(gv + crow(p.v, jj), f);
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const float e = sc[i][jj];
+    for (int x = 0; x < R; ++x) {
+      if (x < nr) {
 #pragma unroll
-      for (int u = 0; u < VE; ++u) acc[i][u] = fmaf(e, f[u], acc[i][u]);
+        for (int i = 0; i < N; ++i) {
+          const float e = sc[x][i][jj];
+#pragma unroll
+          for (int u = 0; u < VE; ++u) acc[x][i][u] = fmaf(e, f[u], acc[x][i][u]);
+        }
+      }
     }
   }
+  if constexpr (ROWS) __syncthreads();   // `part` lies over the scores: every thread is done with them
 #pragma unroll
-  for (int i = 0; i < N; ++i)
+  for (int x = 0; x < R; ++x) {
+    if (nkr[x] > 0) {                    // uniform; a chunk wholly past row x writes no partial for it
 #pragma unroll
-    for (int u = 0; u < VE; ++u) part[g][i][c0 + u] = acc[i][u];
-  __syncthreads();
-  const int64_t row = ((int64_t)b * p.H + h) * p.S + s;      // partial index
-  float* wacc = p.ws + row * N * DV;
-  for (int x = tid; x < N * DV; x += kThreads) {
-    const int i = x / DV, c = x % DV;
-    float a = 0.f;
+      for (int i = 0; i < N; ++i)
 #pragma unroll
-    for (int gg = 0; gg < G; ++gg) a += part[gg][i][c];
-    wacc[x] = a;
+        for (int u = 0; u < VE; ++u) part[g][i][c0 + u] = acc[x][i][u];
+      __syncthreads();
+      // partial index: [b][h][s], rows: [b][h][r][s]
+      const int64_t row = ROWS ? (((int64_t)b * p.H + h) * p.Tq + r0 + x) * p.S + s : ((int64_t)b * p.H + h) * p.S + s;
+      float* wacc = p.ws + row * N * DV;
+      for (int y = tid; y < N * DV; y += kThreads) {
+        const int i = y / DV, c = y % DV;
+        float a = 0.f;
+#pragma unroll
+        for (int gg = 0; gg < G; ++gg) a += part[gg][i][c];
+        wacc[y] = a;
+      }
+      if constexpr (ROWS) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+          if (tid == i) {
+            p.ml[row * N * 2 + i * 2] = m[x * N + i];
+            p.ml[row * N * 2 + i * 2 + 1] = l[x * N + i];
+          }
+        __syncthreads();                 // the next row reuses `part`, the next pass the scores under it
+      } else {
+        if (tid < N) {
+          p.ml[row * N * 2 + tid * 2] = m[tid];
+          p.ml[row * N * 2 + tid * 2 + 1] = l[tid];
+        }
+      }
+    }
   }
-  if (tid < N) {
-    p.ml[row * N * 2 + tid * 2] = m[tid];
-    p.ml[row * N * 2 + tid * 2 + 1] = l[tid];
   }
 }
 
 constexpr int kMaxPartials = 2048;            // S * N per (b, h) for the combine's LDS weights
 
-template <class E, int N, int kChunk>
+// ROWS: one workgroup per (b, h, query row r); row r reduces the partials of its own length
+// pos_b + r + 1 as the one-row combine does, and a padding row (r >= count_b) reduces none: zeros
+template <class E, int N, int kChunk, bool ROWS>
 __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p) {
   __shared__ float wgt[kMaxPartials];          // [s][i] = coef_i / L_i * exp(m_is - M_i)
   __shared__ float red[kWaves * N];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int64_t row0 = ((int64_t)b * p.H + h) * p.S;       // partial stride: the launch's S
-  const int S = min((clamp_len(p, b) + kChunk - 1) / kChunk, p.S);  // chunks written this call
+  const int r = ROWS ? blockIdx.z : 0;
+  // partial stride: the launch's S
+  const int64_t row0 = ROWS ? (((int64_t)b * p.H + h) * p.Tq + r) * p.S : ((int64_t)b * p.H + h) * p.S;
+  int len;
+  if constexpr (ROWS) {
+    const RowSpan sp = row_span(p, b);
+    len = r < sp.cnt ? sp.pos + r + 1 : 0;
+  } else {
+    len = clamp_len(p, b);
+  }
+  const int S = min((len + kChunk - 1) / kChunk, p.S);  // chunks written this call
   const float* ml = p.ml + row0 * N * 2;
   float M[N], Ls[N];
 #pragma unroll
@@ -404,7 +520,7 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
     }
   }
   block_reduce<N, false>(Ls, red);             // barriers also publish wgt
-  E* go = reinterpret_cast<E*>(p.o.p) + b * p.o.sb + h * p.o.sh;
+  E* go = reinterpret_cast<E*>(p.o.p) + b * p.o.sb + h * p.o.sh + (ROWS ? r * p.o.st : 0);
   const float* a = p.ws + row0 * N * p.DV;
   float c[N];
 #pragma unroll
@@ -423,9 +539,11 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
 // current length, so the eager path (length = pos + 1) and the graph path
 // (length = t_cap, device length) launch the same chunks and reduce in the same
 // order: their outputs are bitwise equal at every position.
-template <class E, int N, int HS, int DV, bool PG, class C>
+template <class E, int N, int HS, int DV, bool PG, class C, bool ROWS>
 int split_launch(const DecodeParams& p0, hipStream_t st) {
   constexpr int kC = DTA_DECODE_CHUNK;
+  constexpr int R = ROWS ? rows_per_pass<N, C>() : 1;
+  const dim3 gc(p0.H, p0.B, ROWS ? p0.Tq : 1);
   const int64_t s_cap = (p0.ldw + kC - 1) / kC;
   const bool wide = s_cap * p0.H * p0.B >= kWideGrid;
   const int chunk = wide ? 2 * kC : kC;
@@ -434,23 +552,37 @@ int split_launch(const DecodeParams& p0, hipStream_t st) {
   DecodeParams p = p0;
   p.S = (p0.L + chunk - 1) / chunk;            // same partial layout as C-key chunks, fewer rows used
   if (wide) {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * kC, PG, C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
-    hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * kC>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * kC, PG, C, R>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * kC, ROWS>), gc, dim3(kThreads), 0, st, p);
   } else {
-    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, kC, PG, C>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
-    hipLaunchKernelGGL((decode_combine_kernel<E, N, kC>), dim3(p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, kC, PG, C, R>), dim3(p.S, p.H, p.B), dim3(kThreads), 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, kC, ROWS>), gc, dim3(kThreads), 0, st, p);
   }
   return (int)hipGetLastError();
 }
 
-template <class E, int N, bool PG, class C>
+template <class E, int N, bool PG, class C, bool ROWS = false>
 int split_dispatch(const DecodeParams& p, hipStream_t st) {
-  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64, PG, C>(p, st);
-  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128, PG, C>(p, st);
-  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256, PG, C>(p, st);
-  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64, PG, C>(p, st);
-  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128, PG, C>(p, st);
+  if (p.HS == 32 && p.DV == 64) return split_launch<E, N, 32, 64, PG, C, ROWS>(p, st);
+  if (p.HS == 64 && p.DV == 128) return split_launch<E, N, 64, 128, PG, C, ROWS>(p, st);
+  if (p.HS == 128 && p.DV == 256) return split_launch<E, N, 128, 256, PG, C, ROWS>(p, st);
+  if (N == 1 && p.HS == 64 && p.DV == 64) return split_launch<E, N, 64, 64, PG, C, ROWS>(p, st);
+  if (N == 1 && p.HS == 128 && p.DV == 128) return split_launch<E, N, 128, 128, PG, C, ROWS>(p, st);
   return 1;    // no split plan: caller uses the single-pass kernel
+}
+
+// the multi-row step has the split plan only: no plan (shape, or too many partials for the
+// combine's LDS weights) is unsupported, never a slower kernel
+template <class E, bool PG, class C = E>
+int rows_launch(const DecodeParams& p, hipStream_t st) {
+  int e = 1;
+  switch (p.N) {
+    case 1: e = split_dispatch<E, 1, PG, C, true>(p, st); break;
+    case 2: e = split_dispatch<E, 2, PG, C, true>(p, st); break;
+    case 3: e = split_dispatch<E, 3, PG, C, true>(p, st); break;
+    case 4: e = split_dispatch<E, 4, PG, C, true>(p, st); break;
+  }
+  return e == 1 ? -2 : e;
 }
 
 template <class E, bool PG, class C = E>
@@ -496,6 +628,35 @@ int launch_decode_f8(int dtype, const DecodeParams& p, hipStream_t st) {
     case 0: return decode_launch<__bf16, true, f8e4>(p, st);
     case 1: return decode_launch<_Float16, true, f8e4>(p, st);
     case 2: return decode_launch<float, true, f8e4>(p, st);
+  }
+  return -2;
+}
+
+bool decode_rows_supported(int dtype, int hs, int n, int dv, int tq) {
+  if (dtype < 0 || dtype > 2 || n < 1 || n > 4 || tq < 1 || tq > kMaxRows) return false;
+  if ((hs == 32 && dv == 64) || (hs == 64 && dv == 128) || (hs == 128 && dv == 256)) return true;
+  return n == 1 && dv == hs && (hs == 64 || hs == 128);
+}
+
+int launch_decode_rows(int dtype, const DecodeParams& p, hipStream_t st) {
+  if ((int64_t)p.B * p.H == 0) return 0;
+  if (!p.pos_dev || !p.ml || !decode_rows_supported(dtype, p.HS, p.N, p.DV, p.Tq)) return -2;
+  switch (dtype) {
+    case 0: return p.pg.tbl ? rows_launch<__bf16, true>(p, st) : rows_launch<__bf16, false>(p, st);
+    case 1: return p.pg.tbl ? rows_launch<_Float16, true>(p, st) : rows_launch<_Float16, false>(p, st);
+    case 2: return p.pg.tbl ? rows_launch<float, true>(p, st) : rows_launch<float, false>(p, st);
+  }
+  return -2;
+}
+
+int launch_decode_rows_f8(int dtype, const DecodeParams& p, hipStream_t st) {
+  if ((int64_t)p.B * p.H == 0) return 0;
+  if (!p.pg.tbl || !p.kvs) return -2;
+  if (!p.pos_dev || !p.ml || !decode_rows_supported(dtype, p.HS, p.N, p.DV, p.Tq)) return -2;
+  switch (dtype) {
+    case 0: return rows_launch<__bf16, true, f8e4>(p, st);
+    case 1: return rows_launch<_Float16, true, f8e4>(p, st);
+    case 2: return rows_launch<float, true, f8e4>(p, st);
   }
   return -2;
 }

@@ -135,10 +135,19 @@ struct DecodeParams {
   // in bytes) and kvs the fp32 scales [page][row < P][h][N + 1] (index N: V), kvs_sb floats per page
   const float* kvs;
   int64_t kvs_sb;
+  // several query rows per launch (dta_attn_decode_rows*; pos_dev NULL otherwise): q / o hold Tq rows
+  // per (b, h) (st used), row r is the one-row decode at length pos_b + r + 1; L = ldw = the capacity,
+  // ws the partial rows [b][h][r][s][i][DV], ml [b][h][r][s][i][2]
+  int Tq;              // 1 .. 8
+  const int* pos_dev;  // int32 [B]: sequence b's pos, clamped to [0, ldw - Tq]
+  const int* cnt_dev;  // optional int32 [B]: real rows of sequence b, clamped to [0, Tq]; rows past it are written as zeros
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
 int launch_decode_f8(int dtype, const DecodeParams& p, hipStream_t st);   // dtype: q / o; cache rows fp8
+int launch_decode_rows(int dtype, const DecodeParams& p, hipStream_t st);      // split plan only; -2 without one
+int launch_decode_rows_f8(int dtype, const DecodeParams& p, hipStream_t st);
+bool decode_rows_supported(int dtype, int hs, int n, int dv, int tq);
 
 // dta_kv_quant_rows (kv_quant.hip): rows of K_i / V in the activation dtype -> e4m3fn bytes + scales
 struct KvQuantParams {

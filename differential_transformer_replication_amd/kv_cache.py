@@ -87,6 +87,7 @@ class KVCache:
         self.use_graph = os.environ.get("DTA_DECODE_GRAPH", "1") != "0"
         self.kv_dtype = None                       # rows in the projection's dtype (PagedKVCache may differ)
         self.fp8_extend = False                    # PagedKVCache: the multi-row step of an fp8 pool is one extend launch
+        self.rows_decode = False                   # ragged / paged: a step of 2 .. 8 rows is one split-key decode launch
 
     def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
         buf = self.rows.get(layer)
@@ -390,8 +391,11 @@ class RaggedKVCache(KVCache):
     it exact without a sync: ``host_lengths`` is then an upper bound (``host_exact`` is
     False) until ``sync()``."""
 
-    def __init__(self):
+    def __init__(self, rows_decode: bool = False):
         super().__init__()
+        # rows_decode: a step of 2 .. 8 rows is one ops.diff_attention_decode_rows launch where it has
+        # a plan (every row bitwise the one-row decode's); False (the default) keeps the extend kernel
+        self.rows_decode = bool(rows_decode)
         self.use_graph = False                     # the ragged step runs eagerly
         self.store: Dict[int, torch.Tensor] = {}
         self.lengths: Optional[torch.Tensor] = None
@@ -425,6 +429,9 @@ class RaggedKVCache(KVCache):
 
     def extend_rows(self, kv, q, coef, tbl, pos, counts):
         return ops.diff_attention_extend_ragged(q, *kv, coef, pos, counts)
+
+    def rows_rows(self, kv, q, coef, tbl, pos, counts):
+        return ops.diff_attention_decode_rows(q, *kv, coef, pos, counts)
 
     def set_lengths(self, lengths: Sequence[int], device) -> None:
         self.host_lengths = [int(n) for n in lengths]
@@ -469,7 +476,8 @@ def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one
     sequence b's Tn rows sit at pos[b] .. pos[b]+Tn-1, the first counts[b] of them real (pos,
     counts: device int32 (B,); rows: their (B, Tn) long positions, clamped to the window).
     The cache writes the new rows (``write_rows``: the padding rows land in its spare row or
-    page) and names the op that reads them back (``decode_rows``, ``extend_rows``).
+    page) and names the op that reads them back (``decode_rows``, ``extend_rows``, and with
+    ``cache.rows_decode`` ``rows_rows`` for a step of 2 .. 8 rows that has a plan).
     ``pos=None``: the paged cache's right-padded prefill from position 0 (fused training
     forward on the unquantised activations; counts = the prompt lengths)."""
     attn, H, N, hs, dv, bs = _spec(block)
@@ -490,6 +498,9 @@ def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one
         pass
     elif one_row:
         out = cache.decode_rows(kv, q[:, 0], coef, tbl, pos + counts).view(B, 1, H * dv)
+    elif (cache.rows_decode and 2 <= Tn <= ops.DECODE_ROWS_MAX
+          and ops.decode_rows_supported(qkv.dtype, hs, N, dv, Tn, fp8=cache.kv_dtype is not None)):
+        out = cache.rows_rows(kv, q, coef, tbl, pos, counts)      # a short step: the cache is read once
     elif (ops.extend_supported(qkv.dtype, hs, N, dv) if cache.kv_dtype is None
           else cache.fp8_extend and ops.extend_fp8_supported(qkv.dtype, hs, N, dv)):
         out = cache.extend_rows(kv, q, coef, tbl, pos, counts)
@@ -756,7 +767,7 @@ class PagedKVCache(KVCache):
     KV_DTYPES = (None, "fp8_e4m3")
 
     def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None,
-                 fp8_extend: bool = False):
+                 fp8_extend: bool = False, rows_decode: bool = False):
         super().__init__()
         if page_size not in ops.PAGE_SIZES:
             raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
@@ -772,6 +783,9 @@ class PagedKVCache(KVCache):
         # where it has a plan; False (the default) keeps one decode launch per row.
         self.kv_dtype = kv_dtype
         self.fp8_extend = bool(fp8_extend)
+        # rows_decode: a step of 2 .. 8 rows is one ops.diff_attention_decode_rows_paged(_fp8) launch where
+        # it has a plan, on either kind of pool (it comes before fp8_extend); False (the default) changes nothing
+        self.rows_decode = bool(rows_decode)
         self.scale_pool: Dict[int, torch.Tensor] = {}
         if num_pages < 1:
             raise ValueError("num_pages must be >= 1")
@@ -851,6 +865,11 @@ class PagedKVCache(KVCache):
         if self.kv_dtype is None:
             return ops.diff_attention_extend_paged(q, *kv, coef, tbl, pos, counts)
         return ops.diff_attention_extend_paged_fp8(q, *kv, coef, tbl, pos, counts)
+
+    def rows_rows(self, kv, q, coef, tbl, pos, counts):
+        if self.kv_dtype is None:
+            return ops.diff_attention_decode_rows_paged(q, *kv, coef, tbl, pos, counts)
+        return ops.diff_attention_decode_rows_paged_fp8(q, *kv, coef, tbl, pos, counts)
 
     def cache_bytes(self) -> int:
         """Bytes the pools of every layer hold (spare pages included)."""
@@ -1126,7 +1145,8 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
 
 @torch.no_grad()
 def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
-                   n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None):
+                   n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
+                   rows_decode: bool = False):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1137,7 +1157,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     sample first writes into it); the batch is sample-major within a prompt, and the
     result is a list of B lists of ``n_samples`` tensors.  ``num_pages``: the pool size;
     default the exact need of the call (``OutOfPages`` if a given one is too small).
-    ``kv_dtype``: ``PagedKVCache``'s (``"fp8_e4m3"``: the pages hold e4m3fn bytes and scales)."""
+    ``kv_dtype``: ``PagedKVCache``'s (``"fp8_e4m3"``: the pages hold e4m3fn bytes and scales);
+    ``rows_decode``: ``PagedKVCache``'s, for the multi-row steps made on the cache."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1152,7 +1173,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
             shared = n // page_size if end > n else -(-n // page_size)         # nothing written: all pages shared
             num_pages += shared + n_samples * (-(-end // page_size) - shared)
         num_pages = max(num_pages, 1)
-    cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype)
+    cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype,
+                          rows_decode=rows_decode)
     roots, logits = prefill_paged(model, prompts, cache)
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]

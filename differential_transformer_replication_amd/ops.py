@@ -752,13 +752,16 @@ def extend_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
 
 def _extend(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos: Optional[int] = None,
             pos_dev: Optional[Tensor] = None, counts: Optional[Tensor] = None, page=None,
-            scale_pool: Optional[Tensor] = None) -> Tensor:
+            scale_pool: Optional[Tensor] = None, rows: bool = False) -> Tensor:
     """The tail every extend op ends in, on views its caller has checked: the kernel-plan check
     (no fallback), then the launch.  ``pos``: the host position of ``dta_attn_extend``;
     ``pos_dev`` / ``counts``: the ragged entry point's, with ``page`` = (block_table, P,
-    max_pages, n_pages) the paged one's and with ``scale_pool`` the fp8 one's."""
+    max_pages, n_pages) the paged one's and with ``scale_pool`` the fp8 one's.  ``rows``: the
+    same step on the split-key decode plan (``dta_attn_decode_rows*``, ragged forms only)."""
     B, Tq, H, N, hs = q.shape
     dv = v.shape[-1]
+    if rows:
+        return _decode_rows(lib, q, k, v, coef, T_cap, pos_dev, counts, page, scale_pool)
     if not (extend_supported if scale_pool is None else extend_fp8_supported)(q.dtype, hs, N, dv):
         raise RuntimeError(f"no extend kernel plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}"
                            + ("" if scale_pool is None else " on an fp8 pool"))
@@ -783,6 +786,42 @@ def _extend(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos:
         else:
             rc = lib.dta_attn_extend_paged_fp8(
                 _lib.ExtendPagedFp8Args(*head, *mid, *tail, scale_pool.data_ptr(), scale_pool.stride(0)), stream)
+    _lib.check(rc)
+    return o.view(B, Tq, H * dv)
+
+
+def _decode_rows(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, T_cap: int, pos_dev: Tensor,
+                 counts: Optional[Tensor], page, scale_pool: Optional[Tensor]) -> Tensor:
+    """``_extend``'s launch on the split-key decode plan: the plan check (no fallback), the
+    workspace, then ``dta_attn_decode_rows`` / ``_paged`` / ``_paged_fp8``."""
+    B, Tq, H, N, hs = q.shape
+    dv = v.shape[-1]
+    if not _lib.rows_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no multi-row decode entry points (decode_rows_supported)")
+    if not 1 <= Tq <= DECODE_ROWS_MAX:
+        raise RuntimeError(f"the multi-row decode takes 1 .. {DECODE_ROWS_MAX} rows per sequence, got {Tq}")
+    if not decode_rows_supported(q.dtype, hs, N, dv, Tq, fp8=scale_pool is not None):
+        raise RuntimeError(f"no multi-row decode plan for head_size {hs}, n_terms {N}, dv {dv}, {q.dtype}")
+    coef = coef.detach().to(torch.float32).contiguous()
+    o = torch.empty(B, Tq, H, dv, device=q.device, dtype=q.dtype)
+    if B * H == 0:
+        return o.view(B, Tq, H * dv)
+    nbytes = lib.dta_attn_decode_rows_workspace_bytes(B, H, N, hs, dv, T_cap, Tq)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    head = (_lib.dtype_code(q.dtype), B, H, N, hs, dv, Tq, T_cap, 1.0 / math.sqrt(hs),
+            _lib.tensor5(q), _lib.tensor5(k), _lib.tensor5(v), _lib.tensor5(o),
+            coef.data_ptr(), ws.data_ptr(), pos_dev.data_ptr(), _lib.ptr(counts))
+    stream = _lib.stream_handle(q.device)
+    if page is None:
+        rc = lib.dta_attn_decode_rows(_lib.DecodeRowsArgs(*head), stream)
+    else:
+        table, P, max_pages, n_pages = page
+        tail = (P, max_pages, n_pages, table.data_ptr())
+        if scale_pool is None:
+            rc = lib.dta_attn_decode_rows_paged(_lib.DecodeRowsPagedArgs(*head, *tail), stream)
+        else:
+            rc = lib.dta_attn_decode_rows_paged_fp8(
+                _lib.DecodeRowsPagedFp8Args(*head, *tail, scale_pool.data_ptr(), scale_pool.stride(0)), stream)
     _lib.check(rc)
     return o.view(B, Tq, H * dv)
 
@@ -851,7 +890,7 @@ def diff_attention_decode_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
 
 
 def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: Tensor,
-                                 counts: Optional[Tensor] = None) -> Tensor:
+                                 counts: Optional[Tensor] = None, *, _rows: bool = False) -> Tensor:
     """``diff_attention_extend`` for a batch whose sequences sit at different positions:
     sequence b appends ``counts[b]`` real rows at absolute position ``pos[b]``; row r <
     counts[b] is ``diff_attention_extend``'s row at pos = pos[b], rows r >= counts[b] are
@@ -881,7 +920,7 @@ def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
         _batch_int32(counts, B, q, "counts")
     if Tq > T_cap:
         raise RuntimeError(f"{Tq} new rows do not fit the cache's {T_cap} rows")
-    return _extend(lib, q, k_cache, v_cache, coef, T_cap, pos_dev=pos, counts=counts)
+    return _extend(lib, q, k_cache, v_cache, coef, T_cap, pos_dev=pos, counts=counts, rows=_rows)
 
 
 # ------------------------------------------------------------------- paged ---
@@ -942,7 +981,7 @@ def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
 
 
 def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
-                                pos: Tensor, counts: Optional[Tensor] = None) -> Tensor:
+                                pos: Tensor, counts: Optional[Tensor] = None, *, _rows: bool = False) -> Tensor:
     """``diff_attention_extend_ragged`` over a paged cache (pool views and ``block_table``
     as for ``diff_attention_decode_paged``): sequence b appends ``counts[b]`` real rows at
     ``pos[b]``, its cache rows 0 .. pos[b]+counts[b]-1 reached through its table row
@@ -966,7 +1005,7 @@ def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
     if Tq > T_cap:
         raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
     return _extend(lib, q, k_pool, v_pool, coef, T_cap, pos_dev=pos, counts=counts,
-                   page=(block_table, P, max_pages, n_pages))
+                   page=(block_table, P, max_pages, n_pages), rows=_rows)
 
 
 # --------------------------------------------------------------- fp8 pages ---
@@ -1076,7 +1115,7 @@ def extend_fp8_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
 
 def diff_attention_extend_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
                                     coef: Tensor, block_table: Tensor, pos: Tensor,
-                                    counts: Optional[Tensor] = None) -> Tensor:
+                                    counts: Optional[Tensor] = None, *, _rows: bool = False) -> Tensor:
     """``diff_attention_extend_paged`` over an fp8 page pool, one launch: sequence b appends
     ``counts[b]`` real rows at ``pos[b]`` against its dequantised cache rows 0 ..
     pos[b]+counts[b]-1 (the new rows' own bytes and scales already written, ``kv_quant_rows``).
@@ -1091,7 +1130,7 @@ def diff_attention_extend_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
     included.  Returns (B, Tq, H*dv).  No fallback: raises for a shape without a kernel plan
     or a library without the entry point (``extend_fp8_supported``)."""
     lib = _lib.load()
-    if not _lib.fp8_extend_symbols(lib):
+    if not _rows and not _lib.fp8_extend_symbols(lib):
         raise RuntimeError("this libdiffattn.so has no fp8 extend entry points (extend_fp8_supported)")
     _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
     if q.dim() != 5:
@@ -1110,7 +1149,53 @@ def diff_attention_extend_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
     if Tq > T_cap:
         raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
     return _extend(lib, q, k_pool_u8, v_pool_u8, coef, T_cap, pos_dev=pos, counts=counts,
-                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool)
+                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool, rows=_rows)
+
+
+# ------------------------------------------------- short multi-row steps ---
+# The same step as the ragged extend ops (arguments, checks, clamps, zero padding rows) on the
+# split-key decode plan: one split launch and one combine launch for 1 .. 8 rows per sequence,
+# every cached row loaded once.  Each real row is bitwise the matching one-row decode op at
+# lengths = pos + r + 1.
+DECODE_ROWS_MAX = 8
+
+
+def decode_rows_supported(dtype: torch.dtype, hs: int, N: int, dv: int, Tq: int, fp8: bool = False) -> bool:
+    """Whether ``diff_attention_decode_rows`` (``fp8``: ``..._paged_fp8``) has a kernel plan
+    (dta_decode_rows_supported): the split-key shapes -- (hs, dv) in (32, 64), (64, 128), (128, 256)
+    with N <= 4, or N = 1 with dv = hs in 64, 128 -- at 1 <= Tq <= 8.  False on a library
+    without the entry points."""
+    lib = _lib.load()
+    return _lib.rows_symbols(lib) and bool(
+        lib.dta_decode_rows_supported(_lib.dtype_code(dtype), hs, N, dv, Tq, int(bool(fp8))))
+
+
+def diff_attention_decode_rows(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, pos: Tensor,
+                               counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_extend_ragged``'s step -- q (B, Tq, H, N, hs) padded, ``pos`` / ``counts``
+    device int32 (B,), zeros for rows r >= counts[b] -- for 1 <= Tq <= 8 on the split-key decode
+    plan.  Row r < counts[b] of sequence b is bitwise ``diff_attention_decode_ragged`` at
+    lengths[b] = pos[b] + r + 1.  Cache rows >= pos[b] + counts[b] are never loaded.  Returns
+    (B, Tq, H*dv).  No fallback: raises without a plan (``decode_rows_supported``)."""
+    return diff_attention_extend_ragged(q, k_cache, v_cache, coef, pos, counts, _rows=True)
+
+
+def diff_attention_decode_rows_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
+                                     pos: Tensor, counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_decode_rows`` over a paged cache (arguments of
+    ``diff_attention_extend_paged``); row r is bitwise ``diff_attention_decode_paged`` at
+    lengths[b] = pos[b] + r + 1.  Table entries >= ceil((pos[b] + counts[b]) / P) are not read."""
+    return diff_attention_extend_paged(q, k_pool, v_pool, coef, block_table, pos, counts, _rows=True)
+
+
+def diff_attention_decode_rows_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
+                                         coef: Tensor, block_table: Tensor, pos: Tensor,
+                                         counts: Optional[Tensor] = None) -> Tensor:
+    """``diff_attention_decode_rows_paged`` over an fp8 page pool (arguments of
+    ``diff_attention_extend_paged_fp8``); row r is bitwise ``diff_attention_decode_paged_fp8`` at
+    lengths[b] = pos[b] + r + 1.  Scales of rows >= pos[b] + counts[b] are not read."""
+    return diff_attention_extend_paged_fp8(q, k_pool_u8, v_pool_u8, scale_pool, coef, block_table, pos, counts,
+                                           _rows=True)
 
 
 def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,

@@ -598,6 +598,91 @@ typedef struct dta_attn_extend_paged_fp8_args {
 int dta_attn_extend_paged_fp8(const dta_attn_extend_paged_fp8_args* a, void* stream);
 int dta_extend_fp8_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv);
 
+/* A short multi-row step on the split-key decode plan (still ABI 9; the presence of the
+ * symbols is the capability check): 1 <= Tq <= 8 new rows per sequence -- the verification
+ * of a short draft, the scoring of a few candidate tokens -- in one split launch and one
+ * combine launch that load every cached K_i / V row once for all rows, where Tq
+ * dta_attn_decode_ragged launches each re-read the cache and dta_attn_extend_ragged fills
+ * ceil(Tq/32) * H * B workgroups only.  Replaces the same reference lines as the extend
+ * entries (DiffHead.forward's scores / mask / softmax / combine / @V,
+ * diff_transformer.py:57-72; Ndiff_transformer.py:102-125, for the newest rows only).
+ * For row r of sequence b, with pos_b = pos_dev[b] and count_b = count_dev[b] (NULL: Tq)
+ *   r <  count_b:  o[b][r][h] = sum_i coef[h][i] * softmax_j(q_i[b][r][h] . K_i[b][j][h] * scale, j <= pos_b + r) V[b][j][h]
+ *   r >= count_b:  o[b][r][h] = 0 (q rows count_b .. Tq-1 are never read)
+ * q [b][t < Tq][h][i][d], o [b][t < Tq][h][e], the caches as dta_attn_decode_ragged's
+ * (dta_attn_decode_rows), dta_attn_decode_paged's (_paged) or dta_attn_decode_paged_fp8's
+ * (_paged_fp8, same format and scale placement).  The new rows' own K_i / V are written
+ * first; valid rows of sequence b are 0 .. pos_b + count_b - 1 and nothing above them is
+ * loaded: not K, not V, not a scale, not a page id (entries p >= ceil((pos_b + count_b) /
+ * P)); they may hold anything, NaN included.  count_b == 0 loads nothing at all.
+ * Bitwise relation: every real row equals dta_attn_decode_ragged / _paged / _paged_fp8 at
+ * lengths_dev[b] = pos_b + r + 1 on the same cache at the same t_cap, bit for bit: the chunk
+ * choice from t_cap only, the split of a K row over lanes, the key a thread owns in the
+ * softmax, the V row groups and every order of summation are the one-row kernels'.
+ * Plans: the split-key shapes only -- (head_size, dv) in {(32,64), (64,128), (128,256)} with
+ * n_terms 1..4, and n_terms = 1 with dv = head_size in {64, 128} -- every dtype, 16-/32-bit
+ * or e4m3 cache, while ceil(t_cap/chunk) * n_terms <= 2048.  There is no single-pass plan:
+ * anything else is DTA_ERR_UNSUPPORTED (dta_decode_rows_supported tells beforehand) and the
+ * caller keeps its per-row or extend path.
+ * workspace: fp32, dta_attn_decode_rows_workspace_bytes(.., t_cap, Tq) -- the one-row
+ * split plan's partials and (max, sum) pairs times Tq.
+ * The kernels clamp pos_b to [0, t_cap - Tq], count_b to [0, Tq] and every page id to
+ * [0, n_pages - 1], so no device value can index outside cache, pool, workspace or LDS.
+ * Errors: everything the matching decode / extend entry rejects (null or misaligned
+ * pointers and strides, null pos_dev, t_cap < Tq, the paged and fp8 arguments), and
+ * DTA_ERR_INVALID for Tq outside 1..8.  B*H == 0: DTA_OK, no launch. */
+typedef struct dta_attn_decode_rows_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded), 1 .. 8 */
+  int32_t t_cap;             /* rows of the cache views (>= Tq); sizes the grid and the workspace */
+  float scale;
+  dta_tensor q, k_cache, v_cache, o;
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* pos_dev;    /* device int32 [B], required: absolute position of query row 0 of sequence b */
+  const int32_t* count_dev;  /* device int32 [B] or NULL: real new rows of sequence b */
+} dta_attn_decode_rows_args;
+int dta_attn_decode_rows(const dta_attn_decode_rows_args* a, void* stream);
+size_t dta_attn_decode_rows_workspace_bytes(int32_t B, int32_t H, int32_t n_terms, int32_t head_size, int32_t dv,
+                                            int32_t t_cap, int32_t Tq);
+int dta_decode_rows_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t Tq,
+                              int32_t fp8_cache);
+
+typedef struct dta_attn_decode_rows_paged_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded), 1 .. 8 */
+  int32_t t_cap;             /* = max_pages * page_size (>= Tq) */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* pos_dev;    /* device int32 [B], required */
+  const int32_t* count_dev;  /* device int32 [B] or NULL */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+} dta_attn_decode_rows_paged_args;
+int dta_attn_decode_rows_paged(const dta_attn_decode_rows_paged_args* a, void* stream);
+
+typedef struct dta_attn_decode_rows_paged_fp8_args {
+  int32_t dtype;             /* of q and o */
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t Tq;                /* query rows per sequence (padded), 1 .. 8 */
+  int32_t t_cap;             /* = max_pages * page_size (>= Tq) */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;   /* k_pool / v_pool: e4m3fn bytes, strides in bytes */
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* pos_dev;    /* device int32 [B], required */
+  const int32_t* count_dev;  /* device int32 [B] or NULL */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+  const float* scale_pool_dev;     /* fp32 [page][row < P][h][N+1] */
+  int64_t scale_page_stride;       /* floats from one page's scales to the next */
+} dta_attn_decode_rows_paged_fp8_args;
+int dta_attn_decode_rows_paged_fp8(const dta_attn_decode_rows_paged_fp8_args* a, void* stream);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every
