@@ -38,7 +38,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            "dta_attn_extend_paged_fp8", "dta_extend_fp8_supported",
            # the split-key decode for a step of 2 .. 8 rows, added the same way
            "dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
-           "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
+           "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported",
+           # the shared-prefix decode on the paged cache, added the same way
+           "dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
@@ -47,6 +49,8 @@ FP8_EXTEND_EXPORTS = ("dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
 # and the split-key decode for a step of 2 .. 8 rows (``ops.decode_rows_supported``), added the same way
 ROWS_EXPORTS = ("dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
                 "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
+# and the shared-prefix decode on the paged cache (``ops.decode_shared_supported``), added the same way
+SHARED_EXPORTS = ("dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
 
 
 class DtaTensor(ctypes.Structure):
@@ -174,6 +178,19 @@ class DecodeRowsPagedFp8Args(ctypes.Structure):
                                                ("scale_page_stride", ctypes.c_int64)]
 
 
+# the shared-prefix plan, appended to the paged and the fp8 paged decode structs
+_SHARED_FIELDS = [("n_groups", ctypes.c_int32), ("group_members_dev", ctypes.c_void_p),
+                  ("group_rows_dev", ctypes.c_void_p)]
+
+
+class DecodePagedSharedArgs(ctypes.Structure):
+    _fields_ = DecodePagedArgs._fields_ + _SHARED_FIELDS
+
+
+class DecodePagedSharedFp8Args(ctypes.Structure):
+    _fields_ = DecodePagedFp8Args._fields_ + _SHARED_FIELDS
+
+
 class KvQuantRowsArgs(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Tn", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("n_terms", ctypes.c_int32), ("head_size", ctypes.c_int32), ("dv", ctypes.c_int32),
@@ -252,6 +269,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             for fn in ROWS_EXPORTS:
                 if fn != "dta_attn_decode_rows_workspace_bytes":
                     getattr(lib, fn).restype = ctypes.c_int
+        if shared_symbols(lib):
+            lib.dta_attn_decode_paged_shared.argtypes = [P(DecodePagedSharedArgs), ctypes.c_void_p]
+            lib.dta_attn_decode_paged_shared_fp8.argtypes = [P(DecodePagedSharedFp8Args), ctypes.c_void_p]
+            lib.dta_decode_shared_supported.argtypes = [ctypes.c_int32] * 5
+            for fn in SHARED_EXPORTS:
+                getattr(lib, fn).restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -273,6 +296,12 @@ def rows_symbols(lib) -> bool:
     """Whether ``lib`` exports the multi-row split-key decode entry points (they arrived inside
     ABI 9, after the fp8 extend ones)."""
     return all(hasattr(lib, name) for name in ROWS_EXPORTS)
+
+
+def shared_symbols(lib) -> bool:
+    """Whether ``lib`` exports the shared-prefix decode entry points (they arrived inside ABI 9,
+    after the multi-row decode ones)."""
+    return all(hasattr(lib, name) for name in SHARED_EXPORTS)
 
 
 def check(rc: int) -> None:

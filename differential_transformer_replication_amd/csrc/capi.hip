@@ -576,6 +576,60 @@ int dta_attn_decode_paged_fp8(const dta_attn_decode_paged_fp8_args* a, void* str
   return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, a->scale_pool_dev, a->scale_page_stride);
 }
 
+// ---- shared-prefix decode on the paged cache ----------------------------------------------------
+int dta_decode_shared_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t fp8_cache) {
+  (void)fp8_cache;   // every plan is built for 16-bit, 32-bit and e4m3 pages alike
+  return decode_shared_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
+}
+
+// dta_attn_decode_paged_shared and _fp8: decode_call's checks of the operands, then the plan's
+extern "C++" template <class A>
+static int decode_shared_call(const A* a, const PageTable& pg, void* stream, const float* scales = nullptr,
+                              int64_t scales_sb = 0) {
+  if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (a->n_groups < 0) return DTA_ERR_INVALID;
+  if (a->n_groups > 0 && (!a->group_members_dev || (uintptr_t)a->group_members_dev % 4 || !a->group_rows_dev ||
+                          (uintptr_t)a->group_rows_dev % 4))
+    return DTA_ERR_INVALID;
+  if (!decode_shared_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
+  if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
+  if ((int64_t)a->B * a->H == 0) return DTA_OK;
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
+    return DTA_ERR_INVALID;
+  if (scales ? !ok_byte_pool(a->k_pool, a->head_size, true) || !ok_byte_pool(a->v_pool, a->dv, false)
+             : !ok_tensor(a->k_pool, a->dtype, true) || !ok_tensor(a->v_pool, a->dtype, false))
+    return DTA_ERR_INVALID;
+  DecodeParams p{};
+  p.q = t5(a->q); p.k = t5(a->k_pool); p.v = t5(a->v_pool); p.o = t5(a->o); p.pg = pg;
+  p.coef = a->coef; p.ws = a->workspace;
+  p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
+  p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = a->lengths_dev; p.Lsb = 1;
+  p.S = (int)decode_splits(a->length);
+  p.ml = a->workspace + (int64_t)a->B * a->H * p.S * a->n_terms * a->dv;   // after the partial rows
+  p.sh_g = a->n_groups; p.sh_mem = a->group_members_dev; p.sh_rows = a->group_rows_dev;
+  if (scales) {
+    p.kvs = scales; p.kvs_sb = scales_sb;
+    return status(launch_decode_shared_f8(a->dtype, p, (hipStream_t)stream));
+  }
+  return status(launch_decode_shared(a->dtype, p, (hipStream_t)stream));
+}
+
+int dta_attn_decode_paged_shared(const dta_attn_decode_paged_shared_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
+  return decode_shared_call(a, pg, stream);
+}
+
+int dta_attn_decode_paged_shared_fp8(const dta_attn_decode_paged_shared_fp8_args* a, void* stream) {
+  PageTable pg{};
+  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
+  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
+  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
+    return DTA_ERR_INVALID;
+  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  return decode_shared_call(a, pg, stream, a->scale_pool_dev, a->scale_page_stride);
+}
+
 // ---- split-key decode for a step of 1 .. 8 rows per sequence -----------------------------------
 int dta_decode_rows_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t Tq,
                               int32_t fp8_cache) {

@@ -255,11 +255,55 @@ __device__ __forceinline__ RowSpan row_span(const DecodeParams& p, int b) {
   return r;
 }
 
-template <class E, int N, int HS, int DV, int kChunk, bool PG, class C, int R>
+// ---- shared-prefix plan (dta_attn_decode_paged_shared*) -----------------------------------
+// SH instantiates the R > 1 kernel once more, for the one-row step of a batch in which groups
+// of 2 .. kShared sequences have the same pool pages under their first rows (forks of one
+// prompt): the R rows of a pass are R member sequences of group blockIdx.z, not R consecutive
+// rows of one sequence.  A workgroup runs only for a chunk that lies wholly below the group's
+// covered rows (a multiple of the chunk, at most the shortest member's length), looks the pages
+// up in the first member's table, loads K, V and the scales once, and writes each member's
+// partial into that member's own one-row slot [b][h][s].  No row is masked (the chunk is below
+// every member's length), so every operand and every order is the one-row kernel's on a full
+// chunk.  The one-row pass that follows on the same stream (OWN: the R = 1 kernel with one early
+// exit more) skips the chunks of a sequence below its group's covered rows (own_covered), and
+// the one-row combine reduces what it finds.
+constexpr int kShared = 8;                    // member slots per group
+struct SharedGroup { int first, covered; };   // first valid member (-1: none), covered rows
+// Every device value is clamped before use: a member outside [0, B) is an empty slot, the rows
+// lie in [0, shortest member's clamped length], so nothing at or past `covered` is ever read.
+template <int kChunk>
+__device__ __forceinline__ SharedGroup shared_group(const DecodeParams& p, int g) {
+  SharedGroup r{-1, 0};
+  int lo = p.L;
+  for (int x = kShared - 1; x >= 0; --x) {
+    const int m = p.sh_mem[g * kShared + x];
+    if (m >= 0 && m < p.B) { lo = min(lo, clamp_len(p, m)); r.first = m; }
+  }
+  r.covered = min(max(p.sh_rows[g], 0), lo) / kChunk * kChunk;
+  return r;
+}
+// the rows of sequence b the group pass covered (0: b is in no group); `grp` is one LDS word
+template <int kChunk>
+__device__ __forceinline__ int own_covered(const DecodeParams& p, int b, int* grp) {
+  if (threadIdx.x == 0) *grp = -1;
+  __syncthreads();
+  for (int x = threadIdx.x; x < p.sh_g * kShared; x += kThreads)
+    if (p.sh_mem[x] == b) *grp = x / kShared;
+  __syncthreads();
+  const int g = *grp;
+  return g < 0 ? 0 : shared_group<kChunk>(p, g).covered;
+}
+
+// MODE 0: the kernels of every other entry point; 1: the group pass (SH); 2: the one-row pass of a
+// shared-prefix step (OWN), instantiations of their own so that the MODE 0 kernels stay as they are
+template <class E, int N, int HS, int DV, int kChunk, bool PG, class C, int R, int MODE = 0>
 __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) {
   constexpr bool F8 = is_f8<C>;
   constexpr bool ROWS = R > 1;
+  constexpr bool SH = MODE == 1, OWN = MODE == 2;
   static_assert(!F8 || PG, "the fp8 cache is a paged cache");
+  static_assert(!SH || (PG && ROWS && kShared % R == 0), "the group pass is a paged multi-row pass");
+  static_assert(!OWN || (PG && !ROWS), "the own pass is the paged one-row pass");
   constexpr int KE = F8 ? kF8KB : 8;          // K elements per lane
   constexpr int VE = F8 ? kF8VB : 8;          // V elements per lane
   constexpr int LPR = HS / KE;                // lanes per K row
@@ -274,12 +318,22 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   float (*part)[N][DV + 4] = reinterpret_cast<float (*)[N][DV + 4]>(lds + (ROWS ? 0 : kSc));   // [G][N][DV + 4]
   __shared__ float red[kWaves * N * R];
   __shared__ int pgs[PG ? kChunk / 32 : 1];   // paged: the chunk's pool pages (page size >= 32)
-  const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int s = blockIdx.x, h = blockIdx.y;
+  int b = blockIdx.z;                          // group pass: the group, then its first member (the table read)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j0 = s * kChunk;
-  // L: the keys the workgroup may load (rows: up to the step's last real row; none without one)
+  // L: the keys the workgroup may load (rows: up to the step's last real row; none without one;
+  // group pass: the group's covered rows, a multiple of the chunk)
   int pos = 0, cnt = 1, L;
-  if constexpr (ROWS) {
+  [[maybe_unused]] const int* mem = nullptr;   // group pass: the group's kShared member slots
+  if constexpr (SH) {
+    const SharedGroup sg = shared_group<kChunk>(p, b);
+    if (sg.first < 0) return;
+    mem = p.sh_mem + b * kShared;
+    b = sg.first;
+    cnt = kShared;
+    L = sg.covered;
+  } else if constexpr (ROWS) {
     const RowSpan sp = row_span(p, b);
     pos = sp.pos; cnt = sp.cnt;
     L = cnt ? pos + cnt : 0;
@@ -288,6 +342,10 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   }
   if (j0 >= L) return;                         // grid sized for an upper bound; a chunk past its own
                                                // sequence's length touches no memory (uniform exit)
+  if constexpr (OWN) {
+    // shared-prefix plan: the group pass wrote this chunk's partial (uniform exit, before any cache load)
+    if (j0 < own_covered<kChunk>(p, b, reinterpret_cast<int*>(red))) return;
+  }
   const int nk = min(kChunk, L - j0);
   // paged: the chunk starts on a page boundary (page size divides kChunk); only the pages
   // that hold a row below L are looked up (the rest of the table may hold anything)
@@ -318,26 +376,42 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
   // rows: passes of R rows (one pass, cnt = 1, for the one-row kernel)
   for (int r0 = 0; r0 < cnt; r0 += R) {
   const int nr = ROWS ? min(R, cnt - r0) : 1;   // real rows of this pass
+  // group pass: the member sequence behind row x (-1: an empty slot, which is no row)
+  [[maybe_unused]] int bx[R];
+  if constexpr (SH) {
+    bool any = false;
+#pragma unroll
+    for (int x = 0; x < R; ++x) {
+      const int m = mem[r0 + x];
+      bx[x] = m >= 0 && m < p.B ? m : -1;
+      any |= bx[x] >= 0;
+    }
+    if (!any) continue;                         // uniform
+  }
+  auto live = [&](int x) -> bool {
+    if constexpr (SH) return bx[x] >= 0;
+    else return x < nr;
+  };
   // nkr[x]: the keys of this chunk that row x attends to (0: the chunk lies past the row, or no row)
   int nkr[R];
 #pragma unroll
   for (int x = 0; x < R; ++x)
-    nkr[x] = ROWS ? (x < nr ? min(max(pos + r0 + x + 1 - j0, 0), nk) : 0) : nk;
-  if constexpr (ROWS) {
+    nkr[x] = SH ? (live(x) ? nk : 0) : ROWS ? (x < nr ? min(max(pos + r0 + x + 1 - j0, 0), nk) : 0) : nk;
+  if constexpr (ROWS && !SH) {
     if (pos + r0 + nr <= j0) continue;          // the chunk lies past every row of the pass (uniform)
   }
 
   // phase 1: scores of this chunk into LDS
   {
     const int sub = lane % LPR, kr = lane / LPR;
-    const E* gq = reinterpret_cast<const E*>(p.q.p) + b * p.q.sb + h * p.q.sh + sub * KE;
+    const E* gq = reinterpret_cast<const E*>(p.q.p) + (SH ? 0 : b * p.q.sb) + h * p.q.sh + sub * KE;
     float q[R][N][KE];
 #pragma unroll
     for (int x = 0; x < R; ++x) {
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        if (x < nr) {
-          const E* gx = ROWS ? gq + (int64_t)(r0 + x) * p.q.st : gq;
+        if (live(x)) {
+          const E* gx = SH ? gq + bx[x] * p.q.sb : ROWS ? gq + (int64_t)(r0 + x) * p.q.st : gq;
 #pragma unroll
           for (int c = 0; c < KE; c += 8) ld8f<E>(gx + i * p.q.si + c, q[x][i] + c);
 #pragma unroll
@@ -357,7 +431,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
       for (int i = 0; i < N; ++i) ldnf<C, KE>(kp + i * p.k.si, f[i]);
 #pragma unroll
       for (int x = 0; x < R; ++x) {
-        if (x < nr) {
+        if (live(x)) {
 #pragma unroll
           for (int i = 0; i < N; ++i) {
             float d = 0.f;
@@ -380,7 +454,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       float& mi = m[x * N + i];
-      if (x >= nr) {
+      if (!live(x)) {
         mi = -INFINITY;
       } else if constexpr (F8) {
         // the row's K_i scale: once per (row, branch); rows >= nkr keep their -inf
@@ -405,7 +479,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     for (int i = 0; i < N; ++i) {
       float& li = l[x * N + i];
       li = 0.f;
-      if (x < nr) {
+      if (live(x)) {
 #pragma unroll
         for (int r = 0; r < KPT; ++r) {
           const int j = tid + r * kThreads;
@@ -434,7 +508,7 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
     ldnf<C, VE>(gv + crow(p.v, jj), f);
 #pragma unroll
     for (int x = 0; x < R; ++x) {
-      if (x < nr) {
+      if (live(x)) {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
           const float e = sc[x][i][jj];
@@ -453,8 +527,9 @@ __global__ __launch_bounds__(kThreads) void decode_split_kernel(DecodeParams p) 
 #pragma unroll
         for (int u = 0; u < VE; ++u) part[g][i][c0 + u] = acc[x][i][u];
       __syncthreads();
-      // partial index: [b][h][s], rows: [b][h][r][s]
-      const int64_t row = ROWS ? (((int64_t)b * p.H + h) * p.Tq + r0 + x) * p.S + s : ((int64_t)b * p.H + h) * p.S + s;
+      // partial index: [b][h][s], rows: [b][h][r][s]; group pass: member bx[x]'s own one-row slot
+      const int64_t row = SH ? ((int64_t)bx[x] * p.H + h) * p.S + s
+                        : ROWS ? (((int64_t)b * p.H + h) * p.Tq + r0 + x) * p.S + s : ((int64_t)b * p.H + h) * p.S + s;
       float* wacc = p.ws + row * N * DV;
       for (int y = tid; y < N * DV; y += kThreads) {
         const int i = y / DV, c = y % DV;
@@ -539,16 +614,23 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(DecodeParams p
 // current length, so the eager path (length = pos + 1) and the graph path
 // (length = t_cap, device length) launch the same chunks and reduce in the same
 // order: their outputs are bitwise equal at every position.
+// keys per workgroup of a split launch (0: no plan)
+inline int split_chunk(const DecodeParams& p, int N) {
+  constexpr int kC = DTA_DECODE_CHUNK;
+  const int64_t s_cap = (p.ldw + kC - 1) / kC;
+  const int chunk = s_cap * p.H * p.B >= kWideGrid ? 2 * kC : kC;
+  // the combine keeps one LDS weight per (chunk, branch): gate on the chunk actually launched
+  return ((int64_t)p.ldw + chunk - 1) / chunk * N > kMaxPartials ? 0 : chunk;
+}
+
 template <class E, int N, int HS, int DV, bool PG, class C, bool ROWS>
 int split_launch(const DecodeParams& p0, hipStream_t st) {
   constexpr int kC = DTA_DECODE_CHUNK;
   constexpr int R = ROWS ? rows_per_pass<N, C>() : 1;
   const dim3 gc(p0.H, p0.B, ROWS ? p0.Tq : 1);
-  const int64_t s_cap = (p0.ldw + kC - 1) / kC;
-  const bool wide = s_cap * p0.H * p0.B >= kWideGrid;
-  const int chunk = wide ? 2 * kC : kC;
-  // the combine keeps one LDS weight per (chunk, branch): gate on the chunk actually launched
-  if (((int64_t)p0.ldw + chunk - 1) / chunk * N > kMaxPartials) return 1;
+  const int chunk = split_chunk(p0, N);
+  if (!chunk) return 1;
+  const bool wide = chunk != kC;
   DecodeParams p = p0;
   p.S = (p0.L + chunk - 1) / chunk;            // same partial layout as C-key chunks, fewer rows used
   if (wide) {
@@ -585,6 +667,54 @@ int rows_launch(const DecodeParams& p, hipStream_t st) {
   return e == 1 ? -2 : e;
 }
 
+// A shared-prefix step: the group pass on grid (chunks, H, groups), the one-row pass on (chunks, H,
+// B) and the one-row combine, on the chunk split_launch chooses for the paged call (from t_cap, H
+// and the whole B) and on its partial layout.
+template <class E, int N, int HS, int DV, class C>
+int group_launch(const DecodeParams& p0, hipStream_t st) {
+  constexpr int kC = DTA_DECODE_CHUNK;
+  constexpr int R = rows_per_pass<N, C>();
+  const int chunk = split_chunk(p0, N);
+  if (!chunk) return 1;
+  DecodeParams p = p0;
+  p.S = (p0.L + chunk - 1) / chunk;
+  const dim3 gg(p.S, p.H, p.sh_g), go(p.S, p.H, p.B), gc(p.H, p.B), th(kThreads);
+  if (chunk != kC) {
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * kC, true, C, R, 1>), gg, th, 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, 2 * kC, true, C, 1, 2>), go, th, 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, 2 * kC, false>), gc, th, 0, st, p);
+  } else {
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, kC, true, C, R, 1>), gg, th, 0, st, p);
+    hipLaunchKernelGGL((decode_split_kernel<E, N, HS, DV, kC, true, C, 1, 2>), go, th, 0, st, p);
+    hipLaunchKernelGGL((decode_combine_kernel<E, N, kC, false>), gc, th, 0, st, p);
+  }
+  return (int)hipGetLastError();
+}
+
+template <class E, int N, class C>
+int group_dispatch(const DecodeParams& p, hipStream_t st) {
+  if (p.HS == 32 && p.DV == 64) return group_launch<E, N, 32, 64, C>(p, st);
+  if (p.HS == 64 && p.DV == 128) return group_launch<E, N, 64, 128, C>(p, st);
+  if (p.HS == 128 && p.DV == 256) return group_launch<E, N, 128, 256, C>(p, st);
+  if constexpr (N == 1) {
+    if (p.HS == 64 && p.DV == 64) return group_launch<E, N, 64, 64, C>(p, st);
+    if (p.HS == 128 && p.DV == 128) return group_launch<E, N, 128, 128, C>(p, st);
+  }
+  return 1;
+}
+
+template <class E, class C = E>
+int groups_launch(const DecodeParams& p, hipStream_t st) {
+  int e = 1;
+  switch (p.N) {
+    case 1: e = group_dispatch<E, 1, C>(p, st); break;
+    case 2: e = group_dispatch<E, 2, C>(p, st); break;
+    case 3: e = group_dispatch<E, 3, C>(p, st); break;
+    case 4: e = group_dispatch<E, 4, C>(p, st); break;
+  }
+  return e == 1 ? -2 : e;
+}
+
 template <class E, bool PG, class C = E>
 int decode_launch(const DecodeParams& p, hipStream_t st) {
   if (p.ml) {
@@ -610,6 +740,9 @@ int decode_launch(const DecodeParams& p, hipStream_t st) {
 
 }  // namespace
 
+// decode_shared.hip compiles this file once more with DTA_DECODE_GROUP_TU defined: the group-pass
+// instantiations and their launchers only, so that the two translation units build side by side.
+#ifndef DTA_DECODE_GROUP_TU
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st) {
   if ((int64_t)p.B * p.H == 0) return 0;
   switch (dtype) {
@@ -660,5 +793,28 @@ int launch_decode_rows_f8(int dtype, const DecodeParams& p, hipStream_t st) {
   }
   return -2;
 }
+
+#else   // DTA_DECODE_GROUP_TU
+bool decode_shared_supported(int dtype, int hs, int n, int dv) { return decode_rows_supported(dtype, hs, n, dv, 1); }
+
+// The one-row step of a paged batch under a shared-prefix plan (without a group: the paged launch
+// itself).  Split plan only: -2 without one, before anything is launched.
+static int shared_launch(int dtype, bool f8, const DecodeParams& p0, hipStream_t st) {
+  if ((int64_t)p0.B * p0.H == 0) return 0;
+  if (!p0.pg.tbl || !p0.ml || (f8 && !p0.kvs) || !decode_shared_supported(dtype, p0.HS, p0.N, p0.DV)) return -2;
+  if (!split_chunk(p0, p0.N)) return -2;
+  const DecodeParams& p = p0;
+  if (p.sh_g <= 0 || !p.sh_mem || !p.sh_rows) return f8 ? launch_decode_f8(dtype, p, st) : launch_decode(dtype, p, st);
+  switch (dtype) {
+    case 0: return f8 ? groups_launch<__bf16, f8e4>(p, st) : groups_launch<__bf16>(p, st);
+    case 1: return f8 ? groups_launch<_Float16, f8e4>(p, st) : groups_launch<_Float16>(p, st);
+    case 2: return f8 ? groups_launch<float, f8e4>(p, st) : groups_launch<float>(p, st);
+  }
+  return -2;
+}
+
+int launch_decode_shared(int dtype, const DecodeParams& p, hipStream_t st) { return shared_launch(dtype, false, p, st); }
+int launch_decode_shared_f8(int dtype, const DecodeParams& p, hipStream_t st) { return shared_launch(dtype, true, p, st); }
+#endif  // DTA_DECODE_GROUP_TU
 
 }  // namespace dta

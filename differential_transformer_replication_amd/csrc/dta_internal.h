@@ -141,9 +141,19 @@ struct DecodeParams {
   int Tq;              // 1 .. 8
   const int* pos_dev;  // int32 [B]: sequence b's pos, clamped to [0, ldw - Tq]
   const int* cnt_dev;  // optional int32 [B]: real rows of sequence b, clamped to [0, Tq]; rows past it are written as zeros
+  // shared-prefix plan (dta_attn_decode_paged_shared*; sh_mem NULL otherwise): sh_g groups of up to 8
+  // sequences whose cache rows 0 .. sh_rows[g] - 1 are the same pool pages; the group pass reads those
+  // rows once per group and the one-row pass of that step skips the chunks it covered
+  int sh_g;
+  const int* sh_mem;   // int32 [sh_g][8]: batch indices, anything outside [0, B) is an empty slot
+  const int* sh_rows;  // int32 [sh_g]: shared rows, clamped to [0, the shortest member's length]
 };
 
 int launch_decode(int dtype, const DecodeParams& p, hipStream_t st);
+// paged / fp8-paged one-row decode under a shared-prefix plan: split plan only; -2 without one
+int launch_decode_shared(int dtype, const DecodeParams& p, hipStream_t st);
+int launch_decode_shared_f8(int dtype, const DecodeParams& p, hipStream_t st);
+bool decode_shared_supported(int dtype, int hs, int n, int dv);
 int launch_decode_f8(int dtype, const DecodeParams& p, hipStream_t st);   // dtype: q / o; cache rows fp8
 int launch_decode_rows(int dtype, const DecodeParams& p, hipStream_t st);      // split plan only; -2 without one
 int launch_decode_rows_f8(int dtype, const DecodeParams& p, hipStream_t st);

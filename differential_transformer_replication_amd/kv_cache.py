@@ -40,7 +40,8 @@ shared pool of fixed-size pages behind a per-sequence block table, with a host a
 ``release`` hands a finished sequence's pages to the next prompt, ``fork`` shares a prompt's
 pages among its continuations (copy on write); ``kv_dtype="fp8_e4m3"`` stores e4m3fn bytes
 with one fp32 scale per (row, head, K_i | V), and with ``fp8_extend=True`` a multi-row step on
-those pages is one ``ops.diff_attention_extend_paged_fp8`` launch per layer.  Both run one step (``_seq_model_step``,
+those pages is one ``ops.diff_attention_extend_paged_fp8`` launch per layer; with ``shared_decode=True`` the
+one-token step reads the pages forked sequences still share once per group (``shared_groups``).  Both run one step (``_seq_model_step``,
 ``_seq_attention_step``); the cache says where the new rows go (``write_rows``) and which op
 reads them back (``decode_rows``, ``extend_rows``).
 """
@@ -88,6 +89,8 @@ class KVCache:
         self.kv_dtype = None                       # rows in the projection's dtype (PagedKVCache may differ)
         self.fp8_extend = False                    # PagedKVCache: the multi-row step of an fp8 pool is one extend launch
         self.rows_decode = False                   # ragged / paged: a step of 2 .. 8 rows is one split-key decode launch
+        self.shared_decode = False                 # PagedKVCache: the one-token step reads forked pages once per group
+        self.shared_plan = None                    # the running decode_paged step's ops.SharedDecodePlan, else None
 
     def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
         buf = self.rows.get(layer)
@@ -738,6 +741,9 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
 
 
 # ----------------------------------------------------------------------- paged ---
+SHARED_MIN_ROWS = 256      # one decode chunk (DTA_DECODE_CHUNK): a group pass covers whole chunks only
+
+
 class OutOfPages(RuntimeError):
     """The pool has fewer free pages than a step needs.  Raised before anything is
     written: the allocator, the tables and the lengths are as they were."""
@@ -767,7 +773,7 @@ class PagedKVCache(KVCache):
     KV_DTYPES = (None, "fp8_e4m3")
 
     def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None,
-                 fp8_extend: bool = False, rows_decode: bool = False):
+                 fp8_extend: bool = False, rows_decode: bool = False, shared_decode: bool = False):
         super().__init__()
         if page_size not in ops.PAGE_SIZES:
             raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
@@ -786,6 +792,12 @@ class PagedKVCache(KVCache):
         # rows_decode: a step of 2 .. 8 rows is one ops.diff_attention_decode_rows_paged(_fp8) launch where
         # it has a plan, on either kind of pool (it comes before fp8_extend); False (the default) changes nothing
         self.rows_decode = bool(rows_decode)
+        # shared_decode: decode_paged plans, on the host, which of its sequences still share their first
+        # pages (forks of one prompt) and each layer's one-row decode reads those pages once per group
+        # (ops.diff_attention_decode_paged_shared(_fp8), bitwise the paged op); False (the default) changes nothing
+        self.shared_decode = bool(shared_decode)
+        self._shared_key = None                    # (sequences, their page lists) the kept plan was made from
+        self._shared_kept = None
         self.scale_pool: Dict[int, torch.Tensor] = {}
         if num_pages < 1:
             raise ValueError("num_pages must be >= 1")
@@ -857,6 +869,12 @@ class PagedKVCache(KVCache):
         return k_all[:npg], v_all[:npg], s_all[:npg]
 
     def decode_rows(self, kv, q, coef, tbl, lengths):
+        plan = self.shared_plan                    # set by decode_paged for its one-row step only
+        if (plan is not None and plan.n_groups and plan.B == q.shape[0] and ops.decode_shared_supported(
+                q.dtype, q.shape[-1], q.shape[-2], kv[1].shape[-1], fp8=self.kv_dtype is not None)):
+            if self.kv_dtype is None:
+                return ops.diff_attention_decode_paged_shared(q, *kv, coef, tbl, lengths, plan)
+            return ops.diff_attention_decode_paged_shared_fp8(q, *kv, coef, tbl, lengths, plan)
         if self.kv_dtype is None:
             return ops.diff_attention_decode_paged(q, *kv, coef, tbl, lengths)
         return ops.diff_attention_decode_paged_fp8(q, *kv, coef, tbl, lengths)
@@ -870,6 +888,45 @@ class PagedKVCache(KVCache):
         if self.kv_dtype is None:
             return ops.diff_attention_decode_rows_paged(q, *kv, coef, tbl, pos, counts)
         return ops.diff_attention_decode_rows_paged_fp8(q, *kv, coef, tbl, pos, counts)
+
+    # ---- shared-prefix plan (host only: no device read, no sync)
+    def shared_groups(self, seqs: Sequence[int]):
+        """Which of ``seqs`` (a step's sequences, in batch order) reach their first rows through
+        the same pool pages.  Sequences are gathered by their first page; a set of more than 8 is
+        cut into sets of at most 8; a set shares the pages its lists have in common from the start,
+        and its shared rows are those pages' rows cut to the smallest ``host_low`` of the set (the
+        exact lower bound of a length, so a device-side ``active`` mask cannot make it too large).
+        Sets of one and sets that share less than one decode chunk are dropped.  Returns
+        (groups of batch indices, shared rows), from ``pages``, ``host_low`` and ``page_size`` alone."""
+        first: Dict[int, List[int]] = {}
+        for b, q in enumerate(seqs):
+            if self.pages[q]:
+                first.setdefault(self.pages[q][0], []).append(b)
+        groups, rows = [], []
+        for members in first.values():
+            for at in range(0, len(members), ops.SHARED_GROUP_MAX):
+                part = members[at:at + ops.SHARED_GROUP_MAX]
+                if len(part) < 2:
+                    continue
+                lists = [self.pages[seqs[b]] for b in part]
+                common = 0
+                while all(len(pl) > common and pl[common] == lists[0][common] for pl in lists):
+                    common += 1
+                n = min(common * self.page_size, min(self.host_low[seqs[b]] for b in part))
+                if n >= SHARED_MIN_ROWS:
+                    groups.append(tuple(part))
+                    rows.append(n)
+        return groups, rows
+
+    def _step_plan(self, seqs: Sequence[int], device):
+        """The step's ``ops.SharedDecodePlan``: the kept one while the step's sequences and their
+        page lists stand as they stood when it was made, else a new one (one upload)."""
+        key = (tuple(seqs), tuple(tuple(self.pages[q]) for q in seqs))
+        if key != self._shared_key:
+            groups, rows = self.shared_groups(seqs)
+            self._shared_kept = ops.shared_decode_plan(groups, rows, len(seqs), device)
+            self._shared_key = key
+        return self._shared_kept
 
     def cache_bytes(self) -> int:
         """Bytes the pools of every layer hold (spare pages included)."""
@@ -1019,6 +1076,7 @@ class PagedKVCache(KVCache):
         self.host_lengths[seq] = self.host_low[seq] = new_length
         self._dirty_lens.add(seq)
         self._trim(seq)
+        self._shared_key = None                    # a kept plan's rows were cut to the lengths before
 
     def fork(self, seq: int) -> int:
         """A new sequence with the same content as ``seq``, sharing every one of its
@@ -1100,7 +1158,12 @@ def decode_paged(model, seqs: Sequence[int], tok: torch.Tensor, cache: PagedKVCa
     cache._prepare_writes(seqs, [min(n + 1, bs) for n in have])
     sl, tbl, pos = _paged_gather(cache, seqs)
     counts = torch.ones_like(pos) if active is None else active.to(torch.int32)
-    logits = _paged_model_step(model, tok, cache, tbl, pos, counts, one_row=True)[:, 0]
+    if cache.shared_decode:                       # copy on write and growth have settled the tables
+        cache.shared_plan = cache._step_plan(seqs, tok.device)
+    try:
+        logits = _paged_model_step(model, tok, cache, tbl, pos, counts, one_row=True)[:, 0]
+    finally:
+        cache.shared_plan = None
     cache.lengths.index_copy_(0, sl, pos + counts)
     for q, n in zip(seqs, have):
         cache.host_lengths[q] = min(n + 1, bs)
@@ -1146,7 +1209,7 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
 @torch.no_grad()
 def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
                    n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
-                   rows_decode: bool = False):
+                   rows_decode: bool = False, shared_decode: bool = False):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1158,7 +1221,9 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     result is a list of B lists of ``n_samples`` tensors.  ``num_pages``: the pool size;
     default the exact need of the call (``OutOfPages`` if a given one is too small).
     ``kv_dtype``: ``PagedKVCache``'s (``"fp8_e4m3"``: the pages hold e4m3fn bytes and scales);
-    ``rows_decode``: ``PagedKVCache``'s, for the multi-row steps made on the cache."""
+    ``rows_decode``: ``PagedKVCache``'s, for the multi-row steps made on the cache;
+    ``shared_decode``: ``PagedKVCache``'s: each token's step reads the pages the samples of a
+    prompt still share once per group of up to 8 samples (same logits, bit for bit)."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1174,7 +1239,7 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
             num_pages += shared + n_samples * (-(-end // page_size) - shared)
         num_pages = max(num_pages, 1)
     cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype,
-                          rows_decode=rows_decode)
+                          rows_decode=rows_decode, shared_decode=shared_decode)
     roots, logits = prefill_paged(model, prompts, cache)
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]

@@ -682,11 +682,12 @@ def rope_rows(src: Tensor, dst: Tensor, table: Tensor) -> None:
 
 def _decode(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, bound: int, T_cap: int,
             length_dev: Optional[Tensor] = None, lengths: Optional[Tensor] = None, page=None,
-            scale_pool: Optional[Tensor] = None) -> Tensor:
+            scale_pool: Optional[Tensor] = None, plan=None) -> Tensor:
     """The launch every decode op ends in, on views its caller has checked.  ``bound``: the host
     length (upper bound), which sizes the grid.  ``lengths`` None: ``dta_attn_decode`` with its
     optional device scalar ``length_dev``; else the ragged entry point, with ``page`` =
-    (block_table, P, max_pages, n_pages) the paged one and with ``scale_pool`` the fp8 one."""
+    (block_table, P, max_pages, n_pages) the paged one and with ``scale_pool`` the fp8 one;
+    ``plan`` (a ``SharedDecodePlan``): the paged entry points' shared-prefix twins."""
     B, H, N, hs = q.shape
     dv = v.shape[-1]
     coef = coef.detach().to(torch.float32).contiguous()
@@ -704,7 +705,14 @@ def _decode(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, bound: int, T_ca
     else:
         table, P, max_pages, n_pages = page
         tail = (lengths.data_ptr(), P, max_pages, n_pages, table.data_ptr())
-        if scale_pool is None:
+        if plan is not None:
+            groups = (plan.n_groups, _lib.ptr(plan.members), _lib.ptr(plan.rows))
+            if scale_pool is None:
+                rc = lib.dta_attn_decode_paged_shared(_lib.DecodePagedSharedArgs(*head, *tail, *groups), stream)
+            else:
+                rc = lib.dta_attn_decode_paged_shared_fp8(_lib.DecodePagedSharedFp8Args(
+                    *head, *tail, scale_pool.data_ptr(), scale_pool.stride(0), *groups), stream)
+        elif scale_pool is None:
             rc = lib.dta_attn_decode_paged(_lib.DecodePagedArgs(*head, *tail), stream)
         else:
             rc = lib.dta_attn_decode_paged_fp8(
@@ -1229,3 +1237,122 @@ def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Te
                              _lib.tensor5(k_new), _lib.tensor5(v_new), _lib.tensor5(k_pool_u8),
                              _lib.tensor5(v_pool_u8), scale_pool.data_ptr(), scale_pool.stride(0), slots.data_ptr())
     _lib.check(lib.dta_kv_quant_rows(a, _lib.stream_handle(k_new.device)))
+
+
+# ------------------------------------------------------ shared-prefix decode ---
+# The one-row paged decode for a batch in which groups of sequences have the same pool pages under
+# their first rows (``PagedKVCache.fork``, ``generate_paged(n_samples=k)``): a group pass reads the
+# shared rows once per group, the one-row pass reads what is left (include/diffattn.h "Shared-prefix
+# decode").  Bitwise ``diff_attention_decode_paged(_fp8)`` on the same inputs.
+SHARED_GROUP_MAX = 8
+
+
+class SharedDecodePlan:
+    """The groups of one decode step on the device: ``members`` int32 (n_groups, 8), batch indices
+    padded with -1; ``rows`` int32 (n_groups,), the rows every member of a group reaches through
+    the same pages.  Built once per step (``shared_decode_plan``) and used by every layer."""
+
+    def __init__(self, B: int, groups, shared_rows, members: Optional[Tensor], rows: Optional[Tensor]):
+        self.B = B
+        self.groups = groups
+        self.shared_rows = shared_rows
+        self.n_groups = len(groups)
+        self.members = members
+        self.rows = rows
+
+
+def shared_decode_plan(groups, shared_rows, B: int, device) -> SharedDecodePlan:
+    """Validate a step's groups on the host and upload them once.  ``groups``: sequences of 2 .. 8
+    distinct batch indices in [0, B), no index in two groups; ``shared_rows[g] >= 0``: cache rows
+    0 .. shared_rows[g]-1 are the same pool pages in the block-table row of every member of group
+    g (the caller's promise: the kernels keep every access in range whatever the plan says, but
+    only a true plan gives the paged op's result)."""
+    groups = [tuple(int(b) for b in g) for g in groups]
+    shared_rows = [int(r) for r in shared_rows]
+    if len(groups) != len(shared_rows):
+        raise ValueError(f"{len(groups)} groups, {len(shared_rows)} shared row counts")
+    seen = set()
+    for g, r in zip(groups, shared_rows):
+        if not 2 <= len(g) <= SHARED_GROUP_MAX:
+            raise ValueError(f"a group has {len(g)} members, outside 2 .. {SHARED_GROUP_MAX}")
+        for b in g:
+            if not 0 <= b < B:
+                raise ValueError(f"member {b} outside the batch of {B}")
+            if b in seen:
+                raise ValueError(f"sequence {b} is named twice")
+            seen.add(b)
+        if r < 0:
+            raise ValueError(f"shared rows {r} < 0")
+    if not groups:
+        return SharedDecodePlan(B, groups, shared_rows, None, None)
+    pad = [list(g) + [-1] * (SHARED_GROUP_MAX - len(g)) for g in groups]
+    both = torch.tensor([x for g in pad for x in g] + shared_rows, dtype=torch.int32).to(device)    # one copy
+    n = len(groups) * SHARED_GROUP_MAX
+    return SharedDecodePlan(B, groups, shared_rows, both[:n].view(-1, SHARED_GROUP_MAX), both[n:])
+
+
+def decode_shared_supported(dtype: torch.dtype, hs: int, N: int, dv: int, fp8: bool = False) -> bool:
+    """Whether ``diff_attention_decode_paged_shared`` (``fp8``: ``..._fp8``) has a kernel plan
+    (dta_decode_shared_supported): the split-key shapes of ``decode_rows_supported``.  False on a
+    library without the entry points."""
+    lib = _lib.load()
+    return _lib.shared_symbols(lib) and bool(
+        lib.dta_decode_shared_supported(_lib.dtype_code(dtype), hs, N, dv, int(bool(fp8))))
+
+
+def _shared_plan(lib, plan, B: int, q: Tensor) -> None:
+    if not _lib.shared_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no shared-prefix decode entry points (decode_shared_supported)")
+    if not isinstance(plan, SharedDecodePlan):
+        raise RuntimeError("plan must be a SharedDecodePlan (shared_decode_plan)")
+    if plan.B != B:
+        raise RuntimeError(f"the plan was made for a batch of {plan.B}, q holds {B}")
+    if plan.n_groups and plan.members.device != q.device:
+        raise RuntimeError(f"the plan lives on {plan.members.device}, q on {q.device}")
+
+
+def diff_attention_decode_paged_shared(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
+                                       lengths: Tensor, plan: SharedDecodePlan,
+                                       max_length: Optional[int] = None) -> Tensor:
+    """``diff_attention_decode_paged`` under a shared-prefix plan: the rows a group shares are
+    loaded once per group.  Arguments, checks, clamps and result as the paged op's; bitwise equal
+    to it where the plan is true.  No fallback: raises without a plan, without a kernel plan for
+    the shape (``decode_shared_supported``) or on a library without the entry points."""
+    lib = _lib.load()
+    _require_gpu(q, k_pool, v_pool, coef)
+    B, H, N, hs = q.shape
+    _shared_plan(lib, plan, B, q)
+    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
+    T_cap = max_pages * P
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    _batch_int32(lengths, B, q, "lengths")
+    if B == 0:
+        return q.new_empty(0, H * dv)            # an empty batch (its tensors have no address to pass)
+    return _decode(lib, q, k_pool, v_pool, coef, max_length, T_cap, lengths=lengths,
+                   page=(block_table, P, max_pages, n_pages), plan=plan)
+
+
+def diff_attention_decode_paged_shared_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
+                                           coef: Tensor, block_table: Tensor, lengths: Tensor,
+                                           plan: SharedDecodePlan, max_length: Optional[int] = None) -> Tensor:
+    """``diff_attention_decode_paged_fp8`` under a shared-prefix plan (bytes and scales of the
+    shared rows loaded once per group); otherwise as ``diff_attention_decode_paged_shared``."""
+    lib = _lib.load()
+    _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
+    B, H, N, hs = q.shape
+    _shared_plan(lib, plan, B, q)
+    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
+    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
+        raise RuntimeError("the pool views do not match q")
+    max_pages = _table_pages(block_table, B, q)
+    T_cap = max_pages * P
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    _batch_int32(lengths, B, q, "lengths")
+    if B == 0:
+        return q.new_empty(0, H * dv)
+    return _decode(lib, q, k_pool_u8, v_pool_u8, coef, max_length, T_cap, lengths=lengths,
+                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool, plan=plan)

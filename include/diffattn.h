@@ -683,6 +683,82 @@ typedef struct dta_attn_decode_rows_paged_fp8_args {
 } dta_attn_decode_rows_paged_fp8_args;
 int dta_attn_decode_rows_paged_fp8(const dta_attn_decode_rows_paged_fp8_args* a, void* stream);
 
+/* Shared-prefix decode on the paged cache (still ABI 9; the presence of the symbols is the
+ * capability check): dta_attn_decode_paged / dta_attn_decode_paged_fp8 for a batch in which
+ * groups of sequences have the same pool pages under their first rows -- the samples of one
+ * prompt after a fork.  Same formula, same reference lines (the per-token full-prefix
+ * recompute of generate(), diff_transformer.py:177-185; Ndiff_transformer.py generate;
+ * control.py:163-171); what changes is that the shared rows are read from memory once per
+ * group instead of once per member.
+ * The plan, on the device:
+ *   n_groups            G >= 0
+ *   group_members_dev   int32 [G][8]: batch indices of the 2 .. 8 members of a group; -1 (any
+ *                       value outside [0, B)) is an empty slot; a sequence is in at most one group
+ *   group_rows_dev      int32 [G]: cache rows 0 .. rows-1 are the same pool pages in every
+ *                       member's block-table row
+ * A sequence in no group is handled exactly as by dta_attn_decode_paged.
+ * Launches, in stream order, on the one-row workspace (dta_attn_decode_workspace_bytes):
+ *   1. group pass, grid (chunks, H, G): a workgroup runs only for a chunk wholly below
+ *      covered_g = floor(min(rows_g, min over members of len_b) / chunk) * chunk, looks the
+ *      chunk's pages up in the first member's table, loads every K_i / V row, scale and page
+ *      id once and writes each member's partial into that member's own one-row slot
+ *   2. the one-row split launch, whose workgroups return before they touch the cache where
+ *      their chunk lies below their sequence's covered rows
+ *   3. the one-row combine, unchanged
+ * Bitwise relation: the chunk is chosen as the one-row launch chooses it (from t_cap, H and
+ * the whole B), and the lane split of a K row, the key a thread owns, the V row groups, every
+ * order of summation and the fp8 scale placement are the one-row kernels'.  Given that the
+ * shared rows are the same pages in every member's table, the output equals
+ * dta_attn_decode_paged / dta_attn_decode_paged_fp8 on the same inputs bit for bit.
+ * Plans: the split-key shapes only, as dta_attn_decode_rows (dta_decode_shared_supported tells
+ * beforehand); anything else is DTA_ERR_UNSUPPORTED and the caller keeps the paged call.
+ * Memory safety: len_b and every page id are clamped as in the paged call; a member index
+ * outside [0, B) is an empty slot; rows_g is clamped to [0, shortest member's length]; no
+ * table entry, page, scale or cache row at or past covered_g is read by the group pass and
+ * nothing outside the members' slots is written.  An inconsistent plan (pages that are not
+ * shared, a sequence in two groups) may give wrong numbers, never an out-of-range access.
+ * Errors: everything the paged entry point rejects, and DTA_ERR_INVALID for n_groups < 0 or,
+ * with n_groups > 0, a null or not 4-byte aligned plan pointer.  B*H == 0: DTA_OK, no launch;
+ * n_groups == 0 is the paged call itself. */
+typedef struct dta_attn_decode_paged_shared_args {
+  int32_t dtype;
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t length;            /* host upper bound of every lengths_dev[b] (<= t_cap); sizes the grid */
+  int32_t t_cap;             /* = max_pages * page_size; workspace row length */
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* lengths_dev;/* device int32 [B], required */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+  int32_t n_groups;
+  const int32_t* group_members_dev;  /* device int32 [n_groups][8] */
+  const int32_t* group_rows_dev;     /* device int32 [n_groups] */
+} dta_attn_decode_paged_shared_args;
+int dta_attn_decode_paged_shared(const dta_attn_decode_paged_shared_args* a, void* stream);
+
+typedef struct dta_attn_decode_paged_shared_fp8_args {
+  int32_t dtype;             /* of q and o */
+  int32_t B, H, n_terms, head_size, dv;
+  int32_t length;
+  int32_t t_cap;
+  float scale;
+  dta_tensor q, k_pool, v_pool, o;   /* k_pool / v_pool: e4m3fn bytes, strides in bytes */
+  const float* coef;         /* fp32 [h][i] */
+  float* workspace;
+  const int32_t* lengths_dev;/* device int32 [B], required */
+  int32_t page_size, max_pages, n_pages;
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages] */
+  const float* scale_pool_dev;     /* fp32 [page][row < P][h][N+1] */
+  int64_t scale_page_stride;       /* floats from one page's scales to the next */
+  int32_t n_groups;
+  const int32_t* group_members_dev;  /* device int32 [n_groups][8] */
+  const int32_t* group_rows_dev;     /* device int32 [n_groups] */
+} dta_attn_decode_paged_shared_fp8_args;
+int dta_attn_decode_paged_shared_fp8(const dta_attn_decode_paged_shared_fp8_args* a, void* stream);
+int dta_decode_shared_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t fp8_cache);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every
