@@ -172,8 +172,9 @@ def _dq_reseeded(case, T, k, v):
 
 
 def _run(case, vals, layout, given=None):
-    """One forward and backward through the C ABI at ``layout``; ``given``: input views the
-    caller laid out (and filled) itself.  Checks (c) and returns the results, contiguous."""
+    """One forward and backward through the C ABI at ``layout``; ``given``: views the caller laid
+    out itself, inputs (which it also filled) or outputs (tests/test_gpu_far_addresses.py).
+    Checks (c) and returns the results, contiguous."""
     from differential_transformer_replication_amd import _lib
     lib = _lib.load()
     dev = vals["q"].device
@@ -181,10 +182,9 @@ def _run(case, vals, layout, given=None):
     N, hs, dv, dt = case.N, case.hs, case.dv, _lib.dtype_code(case.dtype)
     assert lib.dta_supported(dt, hs, N, dv)
     views, arenas = _place(case, B, T, H, layout, dev)
+    views.update(given or {})
     for name in ("q", "k", "v", "do"):
-        if given and name in given:
-            views[name] = given[name]
-        else:
+        if not (given and name in given):
             _fill(views[name], vals[name])
 
     def work(name, *shape):                                     # fp32 outputs and workspaces, contiguous
