@@ -40,7 +40,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            "dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
            "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported",
            # the shared-prefix decode on the paged cache, added the same way
-           "dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
+           "dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported",
+           # the fused row write of a ragged / paged step, added the same way
+           "dta_kv_step_rows")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
@@ -51,6 +53,8 @@ ROWS_EXPORTS = ("dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_
                 "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
 # and the shared-prefix decode on the paged cache (``ops.decode_shared_supported``), added the same way
 SHARED_EXPORTS = ("dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
+# and the fused row write of a ragged / paged step (``ops.kv_step_supported``), added the same way
+STEP_EXPORTS = ("dta_kv_step_rows",)
 
 
 class DtaTensor(ctypes.Structure):
@@ -200,6 +204,18 @@ class KvQuantRowsArgs(ctypes.Structure):
                 ("slot_dev", ctypes.c_void_p)]
 
 
+# dta_kv_step_dest
+KV_STEP_CONTIGUOUS, KV_STEP_PAGED, KV_STEP_SLOTS = 0, 1, 2
+
+
+class KvStepRowsArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("dtype", "B", "Tn", "H", "n_terms", "head_size", "dv", "t_cap", "dest",
+                                               "page_size", "max_pages", "n_pages")]
+                + [(n, DtaTensor) for n in ("q", "k", "v", "q_out", "k_dst", "v_dst")]
+                + [(n, ctypes.c_void_p) for n in ("rope_freqs", "pos_dev", "count_dev", "block_table_dev",
+                                                  "slots_out_dev")])
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -275,6 +291,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.dta_decode_shared_supported.argtypes = [ctypes.c_int32] * 5
             for fn in SHARED_EXPORTS:
                 getattr(lib, fn).restype = ctypes.c_int
+        if step_symbols(lib):
+            lib.dta_kv_step_rows.argtypes = [P(KvStepRowsArgs), ctypes.c_void_p]
+            lib.dta_kv_step_rows.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -302,6 +321,12 @@ def shared_symbols(lib) -> bool:
     """Whether ``lib`` exports the shared-prefix decode entry points (they arrived inside ABI 9,
     after the multi-row decode ones)."""
     return all(hasattr(lib, name) for name in SHARED_EXPORTS)
+
+
+def step_symbols(lib) -> bool:
+    """Whether ``lib`` exports the fused row write of a ragged / paged step (it arrived inside ABI 9,
+    after the shared-prefix decode)."""
+    return all(hasattr(lib, name) for name in STEP_EXPORTS)
 
 
 def check(rc: int) -> None:

@@ -718,6 +718,37 @@ int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream) {
   return status(launch_kv_quant(a->dtype, p, (hipStream_t)stream));
 }
 
+int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream) {
+  if (!a || !ok_dims(a->dtype, a->B, a->Tn, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (a->head_size % 8 || a->dv % 8 || a->head_size > 128 || a->dv > 256 || a->n_terms > 8) return DTA_ERR_UNSUPPORTED;
+  if (a->dest < DTA_KV_STEP_CONTIGUOUS || a->dest > DTA_KV_STEP_SLOTS) return DTA_ERR_INVALID;
+  if (a->t_cap < 1 || a->t_cap > (1 << 30) || a->Tn > (1 << 30)) return DTA_ERR_INVALID;
+  if (!a->pos_dev || (uintptr_t)a->pos_dev % 4 || !a->count_dev || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  const bool slots = a->dest == DTA_KV_STEP_SLOTS;
+  int shift = 0;
+  if (a->dest != DTA_KV_STEP_CONTIGUOUS) {
+    shift = page_shift(a->page_size);
+    if (!shift || a->n_pages < 1 || ((int64_t)a->n_pages + 1) * a->page_size > INT32_MAX || a->max_pages < 1 ||
+        (int64_t)a->max_pages * a->page_size < a->t_cap)
+      return DTA_ERR_INVALID;
+    if (!a->block_table_dev || (uintptr_t)a->block_table_dev % 4) return DTA_ERR_INVALID;
+    if (slots && (!a->slots_out_dev || (uintptr_t)a->slots_out_dev % 4)) return DTA_ERR_INVALID;
+  }
+  if ((int64_t)a->B * a->Tn == 0) return DTA_OK;
+  // every view is read or written by 16-byte vector accesses; the views a call does not use are not looked at
+  const bool rope = a->rope_freqs != nullptr;
+  if (rope && (!aligned_ptr(a->rope_freqs) || !ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->q_out, a->dtype, true)))
+    return DTA_ERR_INVALID;
+  if ((rope || !slots) && (!ok_tensor(a->k, a->dtype, true) || !ok_tensor(a->k_dst, a->dtype, true))) return DTA_ERR_INVALID;
+  if (!slots && (!ok_tensor(a->v, a->dtype, false) || !ok_tensor(a->v_dst, a->dtype, false))) return DTA_ERR_INVALID;
+  KvStepParams p{};
+  p.q = t5(a->q); p.k = t5(a->k); p.v = t5(a->v); p.qo = t5(a->q_out); p.kd = t5(a->k_dst); p.vd = t5(a->v_dst);
+  p.freqs = a->rope_freqs; p.pos = a->pos_dev; p.cnt = a->count_dev; p.tbl = a->block_table_dev; p.slots = a->slots_out_dev;
+  p.B = a->B; p.Tn = a->Tn; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
+  p.t_cap = a->t_cap; p.kind = a->dest; p.shift = shift; p.max_pages = a->max_pages; p.n_pages = a->n_pages;
+  return status(launch_kv_step(a->dtype, p, (hipStream_t)stream));
+}
+
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }

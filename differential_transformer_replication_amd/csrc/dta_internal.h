@@ -172,6 +172,22 @@ struct KvQuantParams {
 };
 int launch_kv_quant(int dtype, const KvQuantParams& p, hipStream_t st);
 
+// dta_kv_step_rows (kv_step.hip): the RoPE and the cache scatter of a step's rows at per-sequence positions
+struct KvStepParams {
+  T5 q, k, v;          // the step's rows [b][t < Tn][h][i][d] / [b][t < Tn][h][e], element strides
+  T5 qo;               // rotated Q_i, as q (freqs set)
+  T5 kd, vd;           // by kind: the cache [b][t_cap], the pool [page][row < P], or kd = k_out as k (vd unused)
+  const float* freqs;  // the whole fp32 [t_cap][HS/2][2] table, or NULL: no rotation, q is not touched
+  const int* pos;      // device int32 [B], clamped to [0, t_cap]
+  const int* cnt;      // device int32 [B]: real rows of sequence b
+  const int* tbl;      // paged / slots: device int32 [B][max_pages]; every id read is clamped to [0, n_pages - 1]
+  int* slots;          // slots: device int32 [B * Tn] out
+  int B, Tn, H, N, HS, DV;
+  int t_cap, kind;     // kind: dta_kv_step_dest
+  int shift, max_pages, n_pages;   // shift: log2(page size), 0 for the contiguous cache
+};
+int launch_kv_step(int dtype, const KvStepParams& p, hipStream_t st);
+
 struct ExtendParams {
   T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid
   const float* coef;   // [h][i]

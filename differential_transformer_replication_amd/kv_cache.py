@@ -30,7 +30,8 @@ prefills a long prompt in bounded memory (``prefill_chunk``): the first chunk ru
 the fused training forward, every further chunk appends.
 
 Everything above keeps the whole batch at one position (``KVCache.length``).  Two further
-caches keep one length per sequence on the device; they run eagerly, stay within one
+caches keep one length per sequence on the device; they run eagerly unless made with ``graph=True``
+(``SeqDecodeGraph``: the one-token step as one replayed HIP graph), stay within one
 window, and no existing path enters them.  ``RaggedKVCache`` (``prefill_ragged``,
 ``decode_ragged``, ``append_ragged``, ``generate_ragged``) has the same contiguous rows:
 prompts of different lengths generate as one batch, a verification step accepts a different
@@ -43,7 +44,8 @@ with one fp32 scale per (row, head, K_i | V), and with ``fp8_extend=True`` a mul
 those pages is one ``ops.diff_attention_extend_paged_fp8`` launch per layer; with ``shared_decode=True`` the
 one-token step reads the pages forked sequences still share once per group (``shared_groups``).  Both run one step (``_seq_model_step``,
 ``_seq_attention_step``); the cache says where the new rows go (``write_rows``) and which op
-reads them back (``decode_rows``, ``extend_rows``).
+reads them back (``decode_rows``, ``extend_rows``); with ``fused_step=True`` the RoPE and the scatter of a step's
+rows are one ``ops.kv_step_rows`` launch (``step_rows``).
 """
 from __future__ import annotations
 
@@ -59,7 +61,7 @@ from ._compat import mha_out_scale
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
            "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
-           "append_paged", "generate_paged"]
+           "append_paged", "generate_paged", "SeqDecodeGraph"]
 
 
 def enabled(idx: torch.Tensor, model=None) -> bool:
@@ -91,6 +93,8 @@ class KVCache:
         self.rows_decode = False                   # ragged / paged: a step of 2 .. 8 rows is one split-key decode launch
         self.shared_decode = False                 # PagedKVCache: the one-token step reads forked pages once per group
         self.shared_plan = None                    # the running decode_paged step's ops.SharedDecodePlan, else None
+        self.fused_step = False                    # ragged / paged: a step's RoPE and row scatter are one ops.kv_step_rows
+        self.graphs: Dict[tuple, "SeqDecodeGraph"] = {}    # ragged / paged with graph=True: one per (B, mask given)
 
     def layer(self, layer: int, B: int, cap: int, width: int, like: torch.Tensor) -> torch.Tensor:
         buf = self.rows.get(layer)
@@ -273,6 +277,70 @@ class DecodeGraph:
         return self.logits.clone()
 
 
+class SeqDecodeGraph:
+    """``DecodeGraph`` for the caches with per-sequence lengths: the one-token step of ``decode_ragged``
+    or ``decode_paged`` for a batch of B, captured once and replayed for every token.  The static
+    inputs are ``tok`` (B, 1) long, ``counts`` (B,) int32 (1, or the step's ``active`` mask) and, paged,
+    ``slots`` (B,) long: which rows of ``cache.block_table`` / ``cache.lengths`` the step's sequences
+    are, so any subset or order of B live sequences replays the same graph.  Captured: the paged
+    gather of the table rows and lengths, ``_seq_model_step(..., one_row=True)`` and the length update
+    (ragged: ``lengths.add_(counts)`` in place).  The decode launch sizes its grid from the capacity,
+    and every length, position and page id is read on the device, so one graph serves every length.
+    Page growth and copy on write stay on the host, before the replay (``decode_paged``).
+
+    The graph holds the cache's pools (or rows), ``block_table``, ``lengths`` and the per-layer
+    constants of ``cache.consts`` by address: they exist before the capture (any prefill makes them)
+    and are only ever updated in place.  As for ``DecodeGraph`` the model's parameters are assumed
+    fixed while the graph lives.  Warm-up and capture run with ``counts = 0``: an all-inactive step
+    caches nothing and moves no length, so neither changes the cache's content.  One stream only:
+    the graph has no parallel branches."""
+
+    def __init__(self, model, cache: "KVCache", B: int, device, slots: Optional[torch.Tensor] = None):
+        self.paged = slots is not None
+        if not (cache.pool if self.paged else cache.rows) or cache.lengths is None:
+            raise ValueError("a decode graph needs a prefilled cache: its pools are made by the first prefill")
+        self.model, self.cache = model, cache
+        self.tok = torch.zeros(B, 1, dtype=torch.long, device=device)
+        self.counts = torch.zeros(B, dtype=torch.int32, device=device)
+        self.slots = slots.clone() if self.paged else None
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            self._step()
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.logits = self._step()
+
+    def _step(self) -> torch.Tensor:
+        cache = self.cache
+        if self.paged:
+            tbl = cache.block_table.index_select(0, self.slots)
+            pos = cache.lengths.index_select(0, self.slots)
+            logits = _paged_model_step(self.model, self.tok, cache, tbl, pos, self.counts, one_row=True)[:, 0]
+            cache.lengths.index_copy_(0, self.slots, pos + self.counts)
+        else:
+            logits = _ragged_model_step(self.model, self.tok, cache, cache.lengths, self.counts, one_row=True)[:, 0]
+            cache.lengths.add_(self.counts)
+        return logits
+
+    def step(self, tok: torch.Tensor, counts: torch.Tensor, slots: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self.tok.copy_(tok)
+        self.counts.copy_(counts)
+        if self.paged:
+            self.slots.copy_(slots)
+        self.graph.replay()
+        return self.logits.clone()
+
+
+def _seq_graph(model, cache, B: int, masked: bool, device, slots: Optional[torch.Tensor] = None) -> SeqDecodeGraph:
+    """The cache's graph for a batch of B (one per (B, mask given or not)), captured on first use."""
+    g = cache.graphs.get((B, masked))
+    if g is None:
+        g = cache.graphs[(B, masked)] = SeqDecodeGraph(model, cache, B, device, slots)
+    return g
+
+
 def _model_step(model, idx: torch.Tensor, cache: KVCache, pos: int, all_rows: bool = False) -> torch.Tensor:
     """The model's forward (diff_transformer.py:154-175 / Ndiff_transformer.py) over
     positions pos .. pos+T-1 of the window; returns the last row of logits (B, vocab),
@@ -394,12 +462,16 @@ class RaggedKVCache(KVCache):
     it exact without a sync: ``host_lengths`` is then an upper bound (``host_exact`` is
     False) until ``sync()``."""
 
-    def __init__(self, rows_decode: bool = False):
+    def __init__(self, rows_decode: bool = False, graph: bool = False, fused_step: bool = False):
         super().__init__()
         # rows_decode: a step of 2 .. 8 rows is one ops.diff_attention_decode_rows launch where it has
         # a plan (every row bitwise the one-row decode's); False (the default) keeps the extend kernel
         self.rows_decode = bool(rows_decode)
-        self.use_graph = False                     # the ragged step runs eagerly
+        # graph: decode_ragged replays one captured HIP graph per token (SeqDecodeGraph); ``lengths`` then
+        # keeps its storage for the life of the cache.  fused_step: a step's RoPE and row scatter are one
+        # ops.kv_step_rows launch.  Both False (the default): the eager step as it was
+        self.use_graph = bool(graph)
+        self.fused_step = _want_fused_step(fused_step)
         self.store: Dict[int, torch.Tensor] = {}
         self.lengths: Optional[torch.Tensor] = None
         self.host_lengths: List[int] = []
@@ -427,6 +499,18 @@ class RaggedKVCache(KVCache):
                                      _packed_new_rows(qkv, k_rot, nq))
         return buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
 
+    def step_rows(self, layer: int, qkv, dims, bs: int, tbl, pos, counts, freqs):
+        """``fused_step``: what ``_rope_rows_at`` + ``write_rows`` do, as one ``ops.kv_step_rows`` (the
+        padding rows write nothing; the spare row stays untouched).  Returns (the rotated q, or None
+        without RoPE; the (k_rows, v_rows) views ``write_rows`` returns)."""
+        H, N, hs, dv = dims
+        B, _, W = qkv.shape
+        nq = H * N * hs
+        buf = self.layer(layer, B, bs, W - nq, qkv)
+        kv = buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
+        q_rot, _, _ = ops.kv_step_rows(*ops.split_packed(qkv, H, N, hs, dv), pos, counts, bs, freqs, dest=kv)
+        return q_rot, kv
+
     def decode_rows(self, kv, q, coef, tbl, lengths):
         return ops.diff_attention_decode_ragged(q, *kv, coef, lengths)
 
@@ -438,8 +522,21 @@ class RaggedKVCache(KVCache):
 
     def set_lengths(self, lengths: Sequence[int], device) -> None:
         self.host_lengths = [int(n) for n in lengths]
-        self.lengths = torch.tensor(self.host_lengths, dtype=torch.int32, device=device)
+        new = torch.tensor(self.host_lengths, dtype=torch.int32, device=device)
+        if self.use_graph and self.lengths is not None and self.lengths.shape == new.shape \
+                and self.lengths.device == new.device:
+            self.lengths.copy_(new)                # a captured graph reads and advances this storage
+        else:
+            self.graphs.clear()                    # another batch: the rows are reallocated with it
+            self.lengths = new
         self.host_exact = True
+
+    def advance(self, counts: torch.Tensor) -> None:
+        """``lengths += counts`` on the device: in place where a graph may hold the storage."""
+        if self.use_graph:
+            self.lengths.add_(counts)
+        else:
+            self.lengths = self.lengths + counts
 
     def sync(self) -> List[int]:
         """Refresh ``host_lengths`` from the device (one host sync)."""
@@ -465,6 +562,14 @@ class RaggedKVCache(KVCache):
         self.set_lengths(new, self.lengths.device)
 
 
+def _want_fused_step(fused_step) -> bool:
+    """The caches' ``fused_step`` flag; a library without ``dta_kv_step_rows`` cannot honour it."""
+    if fused_step and not ops.kv_step_supported():
+        raise RuntimeError("fused_step=True needs dta_kv_step_rows, which this libdiffattn.so does not export "
+                           "(ops.kv_step_supported); there is no fallback")
+    return bool(fused_step)
+
+
 def _packed_new_rows(qkv, k_rot, nq: int):
     """A step's new cache rows ``[K | V]`` (B, Tn, W - nq): the slice of ``qkv``, or with
     RoPE the rotated K_i next to its V."""
@@ -480,7 +585,9 @@ def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one
     counts: device int32 (B,); rows: their (B, Tn) long positions, clamped to the window).
     The cache writes the new rows (``write_rows``: the padding rows land in its spare row or
     page) and names the op that reads them back (``decode_rows``, ``extend_rows``, and with
-    ``cache.rows_decode`` ``rows_rows`` for a step of 2 .. 8 rows that has a plan).
+    ``cache.rows_decode`` ``rows_rows`` for a step of 2 .. 8 rows that has a plan).  With
+    ``cache.fused_step`` the rotation of q and K_i and the write are one launch (``step_rows``:
+    the same views back, the padding rows written nowhere).
     ``pos=None``: the paged cache's right-padded prefill from position 0 (fused training
     forward on the unquantised activations; counts = the prompt lengths)."""
     attn, H, N, hs, dv, bs = _spec(block)
@@ -489,14 +596,19 @@ def _seq_attention_step(block, x, layer: int, cache, tbl, pos, counts, rows, one
     B, Tn, _ = qkv.shape
     q, k_new, _ = ops.split_packed(qkv, H, N, hs, dv)
     k_rot = None
+    fused = pos is not None and getattr(cache, "fused_step", False)     # a cache class of its own may not know the flag
     if pos is None:
         out = ops.diff_attention(qkv, coef, H, N, hs, None if freqs is None else freqs[:Tn], dv)
         if freqs is not None:
             k_rot = torch.empty(B, Tn, H, N, hs, device=qkv.device, dtype=qkv.dtype)
             ops.rope_rows(k_new, k_rot, freqs[:Tn])
+    elif fused:                                   # RoPE and scatter in one launch; padding rows write nothing
+        q_rot, kv = cache.step_rows(layer, qkv, (H, N, hs, dv), bs, tbl, pos, counts, freqs)
+        q = q if q_rot is None else q_rot
     elif freqs is not None:
         q, k_rot = _rope_rows_at(q, k_new, freqs, rows)
-    kv = cache.write_rows(layer, qkv, k_rot, (H, N, hs, dv), bs, tbl, pos, counts)
+    if not fused:
+        kv = cache.write_rows(layer, qkv, k_rot, (H, N, hs, dv), bs, tbl, pos, counts)
     if pos is None:
         pass
     elif one_row:
@@ -673,8 +785,11 @@ def decode_ragged(model, tok: torch.Tensor, cache: RaggedKVCache, active: Option
         counts = torch.ones_like(cache.lengths)
     else:
         counts = active.to(torch.int32)
-    logits = _ragged_model_step(model, tok, cache, cache.lengths, counts, one_row=True)[:, 0]
-    cache.lengths = cache.lengths + counts
+    if cache.use_graph:
+        logits = _seq_graph(model, cache, B, active is not None, tok.device).step(tok, counts)
+    else:
+        logits = _ragged_model_step(model, tok, cache, cache.lengths, counts, one_row=True)[:, 0]
+        cache.advance(counts)
     cache.host_lengths = [min(n + 1, bs) for n in cache.host_lengths]
     if active is not None:
         cache.host_exact = False
@@ -706,13 +821,14 @@ def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, al
     cnt = _check_counts(counts, range(B), cache.host_lengths, Tn, bs)
     out, cnt_dev = _append_parts(lambda idx, pos, c, last: _ragged_model_step(model, idx, cache, pos, c, last),
                                  cache.lengths, cache.host_lengths, cnt, new_idx, bs, all_rows)
-    cache.lengths = cache.lengths + cnt_dev
+    cache.advance(cnt_dev)
     cache.host_lengths = [n + c for n, c in zip(cache.host_lengths, cnt)]
     return out
 
 
 @torch.no_grad()
-def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None):
+def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
+                    graph: bool = False, fused_step: bool = False):
     """``generate`` for B prompts of different lengths as one batch (any of the three
     models): one ``prefill_ragged``, then one ``decode_ragged`` step per token.  Sampling
     is the reference's (softmax of the last logits, ``torch.multinomial`` over the whole
@@ -725,13 +841,14 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     position: that stays the one-length path's job (``model.generate``).  So this
     raises ``ValueError`` if any ``len(prompts[b]) + max_new_tokens > block_size``.  The
     loop never reads a length back to the host; the one sync is at the end, where
-    ``eos_id`` cuts the outputs."""
+    ``eos_id`` cuts the outputs.  ``graph`` / ``fused_step``: ``RaggedKVCache``'s (each token's step
+    replays one captured HIP graph; its RoPE and row scatter are one launch): same logits, bit for bit."""
     bs = model.block_size
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
                              f"block_size {bs}: the sliding window is the one-length path's job")
-    cache = RaggedKVCache()
+    cache = RaggedKVCache(graph=graph, fused_step=fused_step)
     logits = prefill_ragged(model, prompts, cache)
     if max_new_tokens < 1:
         return [p.clone() for p in prompts]
@@ -773,7 +890,8 @@ class PagedKVCache(KVCache):
     KV_DTYPES = (None, "fp8_e4m3")
 
     def __init__(self, num_pages: int, page_size: int = 64, max_seqs: Optional[int] = None, kv_dtype=None,
-                 fp8_extend: bool = False, rows_decode: bool = False, shared_decode: bool = False):
+                 fp8_extend: bool = False, rows_decode: bool = False, shared_decode: bool = False,
+                 graph: bool = False, fused_step: bool = False):
         super().__init__()
         if page_size not in ops.PAGE_SIZES:
             raise ValueError(f"page_size {page_size} is not one of {ops.PAGE_SIZES}")
@@ -801,7 +919,15 @@ class PagedKVCache(KVCache):
         self.scale_pool: Dict[int, torch.Tensor] = {}
         if num_pages < 1:
             raise ValueError("num_pages must be >= 1")
-        self.use_graph = False                     # the paged step runs eagerly
+        # graph: decode_paged replays one captured HIP graph per token (SeqDecodeGraph; page growth and copy
+        # on write stay on the host, before the replay).  Not with shared_decode: the plan's group count is a
+        # host launch argument that changes between steps.  fused_step: a step's RoPE and row scatter are one
+        # ops.kv_step_rows launch (fp8: followed by ops.kv_quant_rows).  Both False (the default) change nothing
+        if graph and shared_decode:
+            raise ValueError("graph=True cannot be combined with shared_decode=True: the shared plan's group "
+                             "count is a host launch argument that changes between steps")
+        self.use_graph = bool(graph)
+        self.fused_step = _want_fused_step(fused_step)
         self.num_pages, self.page_size = int(num_pages), int(page_size)
         self.max_seqs = int(num_pages if max_seqs is None else max_seqs)
         if self.max_seqs < 1:
@@ -868,8 +994,31 @@ class PagedKVCache(KVCache):
                           (page * P + at % P).to(torch.int32).flatten())
         return k_all[:npg], v_all[:npg], s_all[:npg]
 
+    def step_rows(self, layer: int, qkv, dims, bs: int, tbl, pos, counts, freqs):
+        """``fused_step``: what ``_rope_rows_at`` + ``write_rows`` do, as one ``ops.kv_step_rows`` -- on an
+        fp8 pool that launch makes the rotated K_i and the slots, and ``ops.kv_quant_rows`` runs on them
+        unchanged.  The spare page is never written (fp8: only by the quantiser, with the padding rows).
+        Returns (the rotated q, or None without RoPE; the pool views ``write_rows`` returns)."""
+        H, N, hs, dv = dims
+        W = qkv.shape[-1]
+        nq = H * N * hs
+        P, npg = self.page_size, self.num_pages
+        q, k_new, v_new = ops.split_packed(qkv, H, N, hs, dv)
+        if self.kv_dtype is None:
+            pool = self.layer_pool(layer, W - nq, qkv)
+            kv = pool[:npg, :, :nq].unflatten(-1, (H, N, hs)), pool[:npg, :, nq:].unflatten(-1, (H, dv))
+            q_rot, _, _ = ops.kv_step_rows(q, k_new, v_new, pos, counts, bs, freqs, dest=kv, block_table=tbl)
+            return q_rot, kv
+        pool, scales = self.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
+        k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
+        v_all = pool[..., nq:].unflatten(-1, (H, dv))
+        s_all = scales.unflatten(-1, (H, N + 1))
+        q_rot, k_out, slots = ops.kv_step_rows(q, k_new, v_new, pos, counts, bs, freqs, None, tbl, P, npg)
+        ops.kv_quant_rows(k_new if k_out is None else k_out, v_new, k_all, v_all, s_all, slots)
+        return q_rot, (k_all[:npg], v_all[:npg], s_all[:npg])
+
     def decode_rows(self, kv, q, coef, tbl, lengths):
-        plan = self.shared_plan                    # set by decode_paged for its one-row step only
+        plan = self.shared_plan                   # set by decode_paged for its one-row step only
         if (plan is not None and plan.n_groups and plan.B == q.shape[0] and ops.decode_shared_supported(
                 q.dtype, q.shape[-1], q.shape[-2], kv[1].shape[-1], fp8=self.kv_dtype is not None)):
             if self.kv_dtype is None:
@@ -1156,15 +1305,22 @@ def decode_paged(model, seqs: Sequence[int], tok: torch.Tensor, cache: PagedKVCa
         raise ValueError(f"a sequence is at block_size {bs}: positions are absolute within the window, "
                          "the sliding window is the one-length path's job (last_logits)")
     cache._prepare_writes(seqs, [min(n + 1, bs) for n in have])
-    sl, tbl, pos = _paged_gather(cache, seqs)
-    counts = torch.ones_like(pos) if active is None else active.to(torch.int32)
-    if cache.shared_decode:                       # copy on write and growth have settled the tables
-        cache.shared_plan = cache._step_plan(seqs, tok.device)
-    try:
-        logits = _paged_model_step(model, tok, cache, tbl, pos, counts, one_row=True)[:, 0]
-    finally:
-        cache.shared_plan = None
-    cache.lengths.index_copy_(0, sl, pos + counts)
+    if cache.use_graph:                           # the gather, the step and the length update are the graph's
+        cache._flush()
+        sl = torch.tensor([cache.slot[q] for q in seqs], device=tok.device)
+        counts = (torch.ones(len(seqs), dtype=torch.int32, device=tok.device) if active is None
+                  else active.to(torch.int32))
+        logits = _seq_graph(model, cache, len(seqs), active is not None, tok.device, sl).step(tok, counts, sl)
+    else:
+        sl, tbl, pos = _paged_gather(cache, seqs)
+        counts = torch.ones_like(pos) if active is None else active.to(torch.int32)
+        if cache.shared_decode:                   # copy on write and growth have settled the tables
+            cache.shared_plan = cache._step_plan(seqs, tok.device)
+        try:
+            logits = _paged_model_step(model, tok, cache, tbl, pos, counts, one_row=True)[:, 0]
+        finally:
+            cache.shared_plan = None
+        cache.lengths.index_copy_(0, sl, pos + counts)
     for q, n in zip(seqs, have):
         cache.host_lengths[q] = min(n + 1, bs)
         if active is None and cache.host_low[q] == n:
@@ -1209,7 +1365,8 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
 @torch.no_grad()
 def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
                    n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
-                   rows_decode: bool = False, shared_decode: bool = False):
+                   rows_decode: bool = False, shared_decode: bool = False, graph: bool = False,
+                   fused_step: bool = False):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1223,7 +1380,9 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     ``kv_dtype``: ``PagedKVCache``'s (``"fp8_e4m3"``: the pages hold e4m3fn bytes and scales);
     ``rows_decode``: ``PagedKVCache``'s, for the multi-row steps made on the cache;
     ``shared_decode``: ``PagedKVCache``'s: each token's step reads the pages the samples of a
-    prompt still share once per group of up to 8 samples (same logits, bit for bit)."""
+    prompt still share once per group of up to 8 samples (same logits, bit for bit);
+    ``graph`` / ``fused_step``: ``PagedKVCache``'s (each token's step replays one captured HIP graph; its
+    RoPE and row scatter are one launch; not with ``shared_decode``): same logits, bit for bit."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1239,7 +1398,7 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
             num_pages += shared + n_samples * (-(-end // page_size) - shared)
         num_pages = max(num_pages, 1)
     cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype,
-                          rows_decode=rows_decode, shared_decode=shared_decode)
+                          rows_decode=rows_decode, shared_decode=shared_decode, graph=graph, fused_step=fused_step)
     roots, logits = prefill_paged(model, prompts, cache)
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]

@@ -1239,6 +1239,107 @@ def kv_quant_rows(k_new: Tensor, v_new: Tensor, k_pool_u8: Tensor, v_pool_u8: Te
     _lib.check(lib.dta_kv_quant_rows(a, _lib.stream_handle(k_new.device)))
 
 
+# ------------------------------------------------- fused step row write ---
+def kv_step_supported() -> bool:
+    """Whether the loaded library has ``dta_kv_step_rows`` (an older build of the same ABI may not)."""
+    return _lib.step_symbols(_lib.load())
+
+
+def kv_step_rows(q: Tensor, k_new: Tensor, v_new: Tensor, pos: Tensor, counts: Tensor, t_cap: int,
+                 freqs: Optional[Tensor], dest=None, block_table: Optional[Tensor] = None,
+                 page_size: Optional[int] = None, n_pages: Optional[int] = None):
+    """The RoPE and the cache scatter of a step's rows at per-sequence positions, in one launch
+    (``dta_kv_step_rows``).  q, k_new (B, Tn, H, N, hs) and v_new (B, Tn, H, dv) are the strided
+    views of the packed projection (``split_packed``); row r of sequence b sits at
+    ``at = pos[b] + r`` and is real if ``r < counts[b] and at < t_cap`` (pos, counts: device int32
+    (B,)).  ``freqs``: the whole RoPE table fp32 (t_cap, hs/2, 2), or None.
+
+    With a table every row of q, padding rows included, is rotated to row ``min(at, t_cap - 1)``
+    into a new tensor, and K_i of a real row to row ``at``, bitwise ``rope_rows``.  K_i and V of a
+    real row are stored to the row's place; a padding row stores no K and no V anywhere:
+
+    * ``dest=(k_rows, v_rows)`` (B, t_cap, H, N, hs) / (B, t_cap, H, dv): row ``at`` of sequence b;
+    * ``dest=(k_pool, v_pool)`` (n_pages, P, ...) with ``block_table`` (B, max_pages): row
+      ``at % P`` of page ``block_table[b, at // P]`` (the id is clamped into the views);
+    * ``dest=None`` with ``block_table``, ``page_size`` and ``n_pages`` (an fp8 pool): no pool is
+      written; the rotated K_i goes to a (B, Tn, H, N, hs) temporary and ``slots`` int32 (B * Tn,)
+      gets ``page * P + at % P`` (a padding row: ``n_pages * P + at % P``, in the spare page) --
+      what ``kv_quant_rows`` takes next.
+
+    Returns ``(q_rot, k_out, slots)``: q_rot None without a table (keep ``q``); k_out None unless
+    ``dest`` is None and there is a table (without one ``k_new`` is what to quantise); slots None
+    unless ``dest`` is None.  hs and dv multiples of 8 up to 128 / 256, N <= 8 (``RuntimeError``
+    otherwise: there is no fallback)."""
+    lib = _lib.load()
+    if not _lib.step_symbols(lib):
+        raise RuntimeError("this libdiffattn.so has no dta_kv_step_rows (kv_step_supported)")
+    _require_gpu(q, k_new, v_new, pos, counts)
+    if q.dim() != 5 or k_new.dim() != 5 or v_new.dim() != 4:
+        raise RuntimeError("q and k_new must be (B, Tn, H, N, hs) and v_new (B, Tn, H, dv)")
+    B, Tn, H, N, hs = k_new.shape
+    dv = v_new.shape[-1]
+    if tuple(q.shape) != (B, Tn, H, N, hs) or tuple(v_new.shape) != (B, Tn, H, dv):
+        raise RuntimeError("q, k_new and v_new do not match each other")
+    if not (q.dtype == k_new.dtype == v_new.dtype):
+        raise RuntimeError("q, k_new and v_new must share a dtype")
+    t_cap = int(t_cap)
+    if t_cap < 1:
+        raise RuntimeError(f"t_cap {t_cap} < 1")
+    _batch_int32(pos, B, k_new, "pos")
+    _batch_int32(counts, B, k_new, "counts")
+    dev = k_new.device
+    if freqs is not None:
+        _require_gpu(freqs)
+        if (freqs.dtype != torch.float32 or tuple(freqs.shape) != (t_cap, hs // 2, 2) or not freqs.is_contiguous()
+                or freqs.device != dev):
+            raise RuntimeError(f"freqs must be the whole contiguous fp32 table ({t_cap}, {hs // 2}, 2) on {dev}")
+    kind, P, max_pages, pages = _lib.KV_STEP_CONTIGUOUS, 0, 0, 0
+    if block_table is not None:
+        max_pages = _table_pages(block_table, B, k_new)
+    if dest is None:
+        kind = _lib.KV_STEP_SLOTS
+        if block_table is None or page_size not in PAGE_SIZES or n_pages is None or int(n_pages) < 1:
+            raise RuntimeError(f"dest=None needs block_table, a page_size of {PAGE_SIZES} and n_pages >= 1")
+        P, pages = int(page_size), int(n_pages)
+        k_dst = v_dst = None
+    else:
+        k_dst, v_dst = dest
+        _require_gpu(k_dst, v_dst)
+        if k_dst.dim() != 5 or v_dst.dim() != 4 or k_dst.dtype != k_new.dtype or v_dst.dtype != k_new.dtype \
+                or k_dst.device != dev or v_dst.device != dev:
+            raise RuntimeError("dest must be (k, v) views of 5 and 4 dimensions in the rows' dtype, on their device")
+        if block_table is None:
+            if tuple(k_dst.shape) != (B, t_cap, H, N, hs) or tuple(v_dst.shape) != (B, t_cap, H, dv):
+                raise RuntimeError("the cache views must be (B, t_cap, H, N, hs) and (B, t_cap, H, dv)")
+        else:
+            kind = _lib.KV_STEP_PAGED
+            pages, P = k_dst.shape[0], k_dst.shape[1]
+            if P not in PAGE_SIZES or pages < 1:
+                raise RuntimeError(f"page size {P} is not one of {PAGE_SIZES}, or the pool holds no page")
+            if tuple(k_dst.shape) != (pages, P, H, N, hs) or tuple(v_dst.shape) != (pages, P, H, dv):
+                raise RuntimeError("the pool views must be (n_pages, P, H, N, hs) and (n_pages, P, H, dv)")
+    if kind != _lib.KV_STEP_CONTIGUOUS and max_pages * P < t_cap:
+        raise RuntimeError(f"a table of {max_pages} pages of {P} rows does not reach t_cap {t_cap}")
+    q_rot = k_out = slots = None
+    if freqs is not None:
+        q_rot = torch.empty(B, Tn, H, N, hs, device=dev, dtype=q.dtype)
+    if kind == _lib.KV_STEP_SLOTS:
+        slots = torch.empty(B * Tn, device=dev, dtype=torch.int32)
+        if freqs is not None:
+            k_out = torch.empty(B, Tn, H, N, hs, device=dev, dtype=q.dtype)
+        k_dst = k_out
+    if B * Tn == 0:
+        return q_rot, k_out, slots
+    none = _lib.DtaTensor()
+    view = lambda t: none if t is None else _lib.tensor5(t)          # noqa: E731
+    a = _lib.KvStepRowsArgs(_lib.dtype_code(q.dtype), B, Tn, H, N, hs, dv, t_cap, kind, P, max_pages, pages,
+                            _lib.tensor5(q), _lib.tensor5(k_new), _lib.tensor5(v_new), view(q_rot), view(k_dst),
+                            view(v_dst), _lib.ptr(freqs), pos.data_ptr(), counts.data_ptr(), _lib.ptr(block_table),
+                            _lib.ptr(slots))
+    _lib.check(lib.dta_kv_step_rows(a, _lib.stream_handle(dev)))
+    return q_rot, k_out, slots
+
+
 # ------------------------------------------------------ shared-prefix decode ---
 # The one-row paged decode for a batch in which groups of sequences have the same pool pages under
 # their first rows (``PagedKVCache.fork``, ``generate_paged(n_samples=k)``): a group pass reads the

@@ -71,6 +71,8 @@ extern "C" {
                                   (block-table KV cache over a pool of pages);
                                   still 9, added the same way: dta_attn_decode_paged_fp8, dta_kv_quant_rows
                                   (e4m3fn pages with per-(row, head) scales);
+                                  still 9, added the same way: dta_kv_step_rows (a step's RoPE and cache
+                                  scatter in one launch);
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -758,6 +760,55 @@ typedef struct dta_attn_decode_paged_shared_fp8_args {
 } dta_attn_decode_paged_shared_fp8_args;
 int dta_attn_decode_paged_shared_fp8(const dta_attn_decode_paged_shared_fp8_args* a, void* stream);
 int dta_decode_shared_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv, int32_t fp8_cache);
+
+/* The row write of a ragged / paged step (still ABI 9; the presence of the symbol is the
+ * capability check): the RoPE of a step's new rows and their scatter into the KV cache in one
+ * launch.  In the reference those rows are recomputed with the whole prefix for every token
+ * (diff_transformer.py:177-185; the rotation is Ndiff_transformer.py:11-22, 104-109); on the
+ * KV cache they were a table gather, two dta_rope launches and an index_put_ of gathered
+ * indices (kv_cache._seq_attention_step, write_rows).
+ * q, k [b][t < Tn][h][i][d] and v [b][t < Tn][h][e] are the step's rows (strided views of the
+ * packed projection).  For row r of sequence b
+ *   at = clamp(pos_dev[b], 0, t_cap) + r,   real = r < count_dev[b] && at < t_cap
+ *   q_out[b][r] = RoPE(q[b][r]) at table row min(at, t_cap - 1), for every row, padding rows
+ *                 included (rope_freqs set; NULL: q_out is not touched, the caller keeps q)
+ *   a real row:   K_i (rotated at table row `at` if rope_freqs is set) and V are stored to the
+ *                 row's place, by dest
+ *     DTA_KV_STEP_CONTIGUOUS  k_dst / v_dst [b][t < t_cap]...: row `at` of sequence b
+ *     DTA_KV_STEP_PAGED       k_dst / v_dst a pool [page][row < P]...: row at % P of page
+ *                             block_table_dev[b][at / P], the id clamped to [0, n_pages - 1]
+ *                             before it forms an address
+ *     DTA_KV_STEP_SLOTS       (an fp8 pool) nothing goes to a pool: the rotated K_i goes to
+ *                             k_dst [b][r < Tn]... (a temporary; without rope_freqs k_dst is not
+ *                             touched), v_dst is unused, and slots_out_dev[b * Tn + r] =
+ *                             page * P + at % P, for a padding row n_pages * P + at % P, a slot
+ *                             of the spare page: the slot_dev of dta_kv_quant_rows, which runs next
+ *   a padding row stores no K and no V anywhere.
+ * The rotation is dta_rope's, bit for bit (the same fp32 expressions in the same order).
+ * rope_freqs is the whole fp32 [t_cap][head_size/2][2] table.  One thread moves 8 elements by
+ * 16-byte accesses; every offset is 64-bit.
+ * DTA_ERR_UNSUPPORTED: head_size or dv not a multiple of 8 (or above 128 / 256), n_terms > 8.
+ * DTA_ERR_INVALID: dest outside the enum, t_cap < 1 or above 2^30, a null or not 4-byte aligned
+ * pos_dev / count_dev, a view whose pointer or strides are not multiples of 16 bytes; paged and
+ * slots: a page_size outside {32, 64, 128, 256}, n_pages < 1, max_pages * page_size < t_cap, a
+ * null or misaligned block_table_dev (slots: slots_out_dev).  B * Tn == 0: DTA_OK, no launch. */
+enum dta_kv_step_dest { DTA_KV_STEP_CONTIGUOUS = 0, DTA_KV_STEP_PAGED = 1, DTA_KV_STEP_SLOTS = 2 };
+typedef struct dta_kv_step_rows_args {
+  int32_t dtype;
+  int32_t B, Tn, H, n_terms, head_size, dv;
+  int32_t t_cap;             /* rows of a sequence's window: the table's rows, the bound of `at` */
+  int32_t dest;              /* dta_kv_step_dest */
+  int32_t page_size, max_pages, n_pages;   /* paged and slots (0 otherwise) */
+  dta_tensor q, k, v;
+  dta_tensor q_out;          /* as q; used with rope_freqs only */
+  dta_tensor k_dst, v_dst;
+  const float* rope_freqs;   /* fp32 [t_cap][head_size/2][2], or NULL */
+  const int32_t* pos_dev;    /* device int32 [B] */
+  const int32_t* count_dev;  /* device int32 [B] */
+  const int32_t* block_table_dev;  /* device int32 [B][max_pages]; paged and slots */
+  int32_t* slots_out_dev;    /* device int32 [B * Tn]; slots */
+} dta_kv_step_rows_args;
+int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream);
 
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
