@@ -42,7 +42,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # the shared-prefix decode on the paged cache, added the same way
            "dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported",
            # the fused row write of a ragged / paged step, added the same way
-           "dta_kv_step_rows")
+           "dta_kv_step_rows",
+           # seeded temperature / top-k / top-p sampling of logits rows, added the same way
+           "dta_sample_rows")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
@@ -55,6 +57,8 @@ ROWS_EXPORTS = ("dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_
 SHARED_EXPORTS = ("dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
 # and the fused row write of a ragged / paged step (``ops.kv_step_supported``), added the same way
 STEP_EXPORTS = ("dta_kv_step_rows",)
+# and the row sampler (``ops.sample_supported``), added the same way
+SAMPLE_EXPORTS = ("dta_sample_rows",)
 
 
 class DtaTensor(ctypes.Structure):
@@ -216,6 +220,15 @@ class KvStepRowsArgs(ctypes.Structure):
                                                   "slots_out_dev")])
 
 
+class SampleRowsArgs(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("R", ctypes.c_int32), ("V", ctypes.c_int32),
+                ("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64),
+                ("temperature", ctypes.c_float), ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float),
+                ("temperature_dev", ctypes.c_void_p), ("top_k_dev", ctypes.c_void_p), ("top_p_dev", ctypes.c_void_p),
+                ("seed", ctypes.c_uint64), ("stream_dev", ctypes.c_void_p), ("offset_dev", ctypes.c_void_p),
+                ("token_out", ctypes.c_void_p), ("logprob_out", ctypes.c_void_p)]
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -294,6 +307,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if step_symbols(lib):
             lib.dta_kv_step_rows.argtypes = [P(KvStepRowsArgs), ctypes.c_void_p]
             lib.dta_kv_step_rows.restype = ctypes.c_int
+        if sample_symbols(lib):
+            lib.dta_sample_rows.argtypes = [P(SampleRowsArgs), ctypes.c_void_p]
+            lib.dta_sample_rows.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -327,6 +343,11 @@ def step_symbols(lib) -> bool:
     """Whether ``lib`` exports the fused row write of a ragged / paged step (it arrived inside ABI 9,
     after the shared-prefix decode)."""
     return all(hasattr(lib, name) for name in STEP_EXPORTS)
+
+
+def sample_symbols(lib) -> bool:
+    """Whether ``lib`` exports the row sampler (it arrived inside ABI 9, after the fused row write)."""
+    return all(hasattr(lib, name) for name in SAMPLE_EXPORTS)
 
 
 def check(rc: int) -> None:

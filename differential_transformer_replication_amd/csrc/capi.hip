@@ -749,6 +749,31 @@ int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream) {
   return status(launch_kv_step(a->dtype, p, (hipStream_t)stream));
 }
 
+// this library is built with -fno-honor-nans: x != x folds away, the bits do not
+static bool nan_bits(float x) {
+  uint32_t b;
+  __builtin_memcpy(&b, &x, 4);
+  return (b & 0x7fffffffu) > 0x7f800000u;
+}
+
+int dta_sample_rows(const dta_sample_rows_args* a, void* stream) {
+  if (!a || a->dtype < DTA_BF16 || a->dtype > DTA_F32 || a->R < 0 || a->V < 1) return DTA_ERR_INVALID;
+  if (nan_bits(a->temperature) || nan_bits(a->top_p)) return DTA_ERR_INVALID;
+  if ((uintptr_t)a->temperature_dev % 4 || (uintptr_t)a->top_k_dev % 4 || (uintptr_t)a->top_p_dev % 4 ||
+      (uintptr_t)a->logprob_out % 4 || (uintptr_t)a->stream_dev % 8 || (uintptr_t)a->offset_dev % 8 ||
+      (uintptr_t)a->token_out % 8)
+    return DTA_ERR_INVALID;
+  if (a->V > (1 << 20)) return DTA_ERR_UNSUPPORTED;
+  if (a->R == 0) return DTA_OK;
+  if (!a->logits || !a->token_out || (uintptr_t)a->logits % (a->dtype == DTA_F32 ? 4 : 2)) return DTA_ERR_INVALID;
+  SampleParams p{};
+  p.logits = a->logits; p.stride = a->row_stride; p.R = a->R; p.V = a->V;
+  p.T = a->temperature; p.k = a->top_k; p.p = a->top_p;
+  p.Tdev = a->temperature_dev; p.kdev = a->top_k_dev; p.pdev = a->top_p_dev;
+  p.seed = a->seed; p.strm = a->stream_dev; p.off = a->offset_dev; p.tok = a->token_out; p.lp = a->logprob_out;
+  return status(launch_sample(a->dtype, p, (hipStream_t)stream));
+}
+
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }

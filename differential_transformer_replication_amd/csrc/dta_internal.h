@@ -188,6 +188,21 @@ struct KvStepParams {
 };
 int launch_kv_step(int dtype, const KvStepParams& p, hipStream_t st);
 
+// dta_sample_rows (sample.hip): one token per logits row, seeded temperature / top-k / top-p sampling
+struct SampleParams {
+  const void* logits;  // [R][V] in the launch's dtype, row stride in elements
+  int64_t stride;
+  int R, V;
+  float T; int k; float p;                     // used where the per-row pointer is NULL
+  const float* Tdev; const int* kdev; const float* pdev;
+  uint64_t seed;
+  const int64_t* strm; // [R] or NULL: the row index
+  const int64_t* off;  // [R] or NULL: 0
+  int64_t* tok;        // [R]
+  float* lp;           // [R] or NULL
+};
+int launch_sample(int dtype, const SampleParams& p, hipStream_t st);
+
 struct ExtendParams {
   T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid
   const float* coef;   // [h][i]

@@ -46,6 +46,10 @@ one-token step reads the pages forked sequences still share once per group (``sh
 ``_seq_attention_step``); the cache says where the new rows go (``write_rows``) and which op
 reads them back (``decode_rows``, ``extend_rows``); with ``fused_step=True`` the RoPE and the scatter of a step's
 rows are one ``ops.kv_step_rows`` launch (``step_rows``).
+
+Every generate loop takes ``sampler=None``: a ``Sampler`` (temperature, top-k, top-p, seed) replaces the
+reference's two sampling lines by one ``ops.sample_rows`` launch per step whose draw for a sequence depends
+on (seed, the sequence's stream, its position) only; None keeps the reference's lines, token for token.
 """
 from __future__ import annotations
 
@@ -61,7 +65,49 @@ from ._compat import mha_out_scale
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
            "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
-           "append_paged", "generate_paged", "SeqDecodeGraph"]
+           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler"]
+
+
+class Sampler:
+    """Opt-in sampling controls of the generate loops: ``temperature`` (``<= 0``: greedy), ``top_k``
+    (``<= 0``: off), ``top_p`` (``>= 1``: off) and ``seed``.  One ``ops.sample_rows`` launch per step
+    draws sequence s's t-th token from Philox(seed, stream=s, offset=t) alone, so its samples do not
+    depend on what else is in the batch.  Immutable; ``sampler=None`` everywhere keeps the
+    reference's softmax + ``torch.multinomial``."""
+    __slots__ = ("temperature", "top_k", "top_p", "seed")
+
+    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
+        if temperature != temperature or top_p != top_p:
+            raise ValueError("temperature and top_p must not be NaN")
+        for name, v in (("temperature", float(temperature)), ("top_k", int(top_k)), ("top_p", float(top_p)),
+                        ("seed", int(seed))):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Sampler is immutable")
+
+    def __repr__(self):
+        return f"Sampler(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, seed={self.seed})"
+
+    def sample(self, logits: torch.Tensor, step: int, streams: Optional[torch.Tensor] = None,
+               return_logprobs: bool = False):
+        """The ``step``-th token of every row of ``logits`` (B, V): (B, 1) int64 (and the (B,) logprobs).
+        ``streams``: int64 (B,) stream ids, default the row index.  The offsets are filled on the
+        device: no host sync, and the same values under a graph-replayed step."""
+        offset = torch.full((logits.shape[0],), step, dtype=torch.int64, device=logits.device)
+        out = ops.sample_rows(logits, self.temperature, self.top_k, self.top_p, self.seed, streams, offset,
+                              return_logprobs)
+        return (out[0][:, None], out[1]) if return_logprobs else out[:, None]
+
+
+def _stream_ids(streams, B: int, n_samples: int, device) -> Optional[torch.Tensor]:
+    """int64 (B * n_samples,) stream ids: ``streams[b] * n_samples + sample`` (None: the row index)."""
+    if streams is None:
+        return None
+    if len(streams) != B:
+        raise ValueError(f"streams must give one id per prompt ({B}), got {len(streams)}")
+    return torch.tensor([int(s) * n_samples + j for s in streams for j in range(n_samples)], dtype=torch.int64,
+                        device=device)
 
 
 def enabled(idx: torch.Tensor, model=None) -> bool:
@@ -436,16 +482,29 @@ def prefill_logits(model, idx: torch.Tensor, cache: KVCache, prefill_chunk=None)
 
 
 @torch.no_grad()
-def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk=None) -> torch.Tensor:
+def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk=None,
+                    sampler: Optional[Sampler] = None) -> torch.Tensor:
     check_prefill_chunk(prefill_chunk)
     cache = KVCache()
-    for _ in range(max_new_tokens):
+    for step in range(max_new_tokens):
         if prefill_chunk is not None and (cache.length == 0 or idx.shape[1] != cache.length + 1):
             logits = prefill_logits(model, idx, cache, prefill_chunk)
         else:
             logits = last_logits(model, idx, cache)
+        if sampler is not None:
+            idx = torch.cat((idx, sampler.sample(logits, step)), dim=1)
+            continue
         probs = F.softmax(logits, dim=-1)
         idx = torch.cat((idx, torch.multinomial(probs, num_samples=1)), dim=1)
+    return idx
+
+
+@torch.no_grad()
+def naive_generate(model, idx: torch.Tensor, max_new_tokens: int, sampler: Sampler) -> torch.Tensor:
+    """The models' full-recompute ``generate`` loop with a ``Sampler`` in place of softmax + multinomial."""
+    for step in range(max_new_tokens):
+        logits, _ = model(idx[:, -model.block_size:])
+        idx = torch.cat((idx, sampler.sample(logits[:, -1, :], step)), dim=1)
     return idx
 
 
@@ -712,9 +771,11 @@ def _append_parts(step, lens, have: Sequence[int], cnt: Sequence[int], new_idx, 
     return out, cnt_dev
 
 
-def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode):
+def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode, sampler: Optional[Sampler] = None,
+                   streams: Optional[torch.Tensor] = None):
     """The reference's sampling loop (softmax of the last logits, one ``torch.multinomial``
-    over the whole batch) for ``max_new_tokens >= 1`` tokens; ``decode(tok, active)`` is the
+    over the whole batch; with a ``sampler``, one ``ops.sample_rows`` launch that draws row b's
+    ``step``-th token from (seed, ``streams[b]`` or b, step)) for ``max_new_tokens >= 1`` tokens; ``decode(tok, active)`` is the
     cache's one-token step, ``active`` the device mask of the sequences that have not
     sampled ``eos_id`` (None without one).  Returns (toks (B, max_new_tokens), keep): sequence
     b keeps its first keep[b] tokens, up to its first ``eos_id`` -- the loop's one host sync."""
@@ -722,8 +783,11 @@ def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode):
     active = None if eos_id is None else torch.ones(B, dtype=torch.bool, device=logits.device)
     new = []
     for step in range(max_new_tokens):
-        probs = F.softmax(logits, dim=-1)
-        tok = torch.multinomial(probs, num_samples=1)
+        if sampler is not None:
+            tok = sampler.sample(logits, step, streams)
+        else:
+            probs = F.softmax(logits, dim=-1)
+            tok = torch.multinomial(probs, num_samples=1)
         new.append(tok)
         if step + 1 == max_new_tokens:
             break
@@ -828,7 +892,8 @@ def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, al
 
 @torch.no_grad()
 def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
-                    graph: bool = False, fused_step: bool = False):
+                    graph: bool = False, fused_step: bool = False, sampler: Optional[Sampler] = None,
+                    streams: Optional[Sequence[int]] = None):
     """``generate`` for B prompts of different lengths as one batch (any of the three
     models): one ``prefill_ragged``, then one ``decode_ragged`` step per token.  Sampling
     is the reference's (softmax of the last logits, ``torch.multinomial`` over the whole
@@ -842,7 +907,11 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     raises ``ValueError`` if any ``len(prompts[b]) + max_new_tokens > block_size``.  The
     loop never reads a length back to the host; the one sync is at the end, where
     ``eos_id`` cuts the outputs.  ``graph`` / ``fused_step``: ``RaggedKVCache``'s (each token's step
-    replays one captured HIP graph; its RoPE and row scatter are one launch): same logits, bit for bit."""
+    replays one captured HIP graph; its RoPE and row scatter are one launch): same logits, bit for bit.
+    ``sampler``: a ``Sampler`` replaces softmax + multinomial by one ``ops.sample_rows`` launch per step,
+    run eagerly after the step or its graph replay; sequence b's t-th token is drawn from (seed,
+    stream b, offset t) -- ``streams`` gives the prompts other stream ids -- so it does not depend on
+    the rest of the batch.  None (the default): the reference's sampling, token for token."""
     bs = model.block_size
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
@@ -853,7 +922,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     if max_new_tokens < 1:
         return [p.clone() for p in prompts]
     toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
-                                lambda tok, active: decode_ragged(model, tok, cache, active))
+                                lambda tok, active: decode_ragged(model, tok, cache, active), sampler,
+                                _stream_ids(streams, len(prompts), 1, logits.device))
     return [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(prompts)]
 
 
@@ -1366,7 +1436,8 @@ def append_paged(model, seqs: Sequence[int], new_idx: torch.Tensor, counts, cach
 def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
                    n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
                    rows_decode: bool = False, shared_decode: bool = False, graph: bool = False,
-                   fused_step: bool = False):
+                   fused_step: bool = False, sampler: Optional[Sampler] = None,
+                   streams: Optional[Sequence[int]] = None):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1382,7 +1453,9 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     ``shared_decode``: ``PagedKVCache``'s: each token's step reads the pages the samples of a
     prompt still share once per group of up to 8 samples (same logits, bit for bit);
     ``graph`` / ``fused_step``: ``PagedKVCache``'s (each token's step replays one captured HIP graph; its
-    RoPE and row scatter are one launch; not with ``shared_decode``): same logits, bit for bit."""
+    RoPE and row scatter are one launch; not with ``shared_decode``): same logits, bit for bit.
+    ``sampler`` / ``streams``: ``generate_ragged``'s; sample j of prompt b draws from stream
+    ``b * n_samples + j`` (``streams[b] * n_samples + j``), so the forks of one prompt differ."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1406,7 +1479,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
         if n_samples > 1:
             logits = logits.repeat_interleave(n_samples, dim=0)
         toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
-                                    lambda tok, active: decode_paged(model, seqs, tok, cache, active))
+                                    lambda tok, active: decode_paged(model, seqs, tok, cache, active), sampler,
+                                    _stream_ids(streams, len(prompts), n_samples, logits.device))
         outs = [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(outs)]
     else:
         outs = [p.clone() for p in outs]

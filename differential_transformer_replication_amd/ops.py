@@ -1340,6 +1340,189 @@ def kv_step_rows(q: Tensor, k_new: Tensor, v_new: Tensor, pos: Tensor, counts: T
     return q_rot, k_out, slots
 
 
+# ------------------------------------------------------------------ sampling ---
+# One token per logits row: temperature, top-k, top-p and a counter-based uniform (Philox4x32-10 of
+# (seed, stream, offset)), so a row's token depends on the row, its parameters and that triple only --
+# not on the batch it is sampled in.  The definition is include/diffattn.h's ("Sampling");
+# ``sample_rows`` is the HIP kernel, ``sample_rows_reference`` the same definition in torch.
+SAMPLE_MAX_V = 1 << 20
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def sample_supported() -> bool:
+    """Whether the loaded library has ``dta_sample_rows`` (an older build of the same ABI may not)."""
+    return _lib.sample_symbols(_lib.load())
+
+
+def _mulhilo32(a: int, b: Tensor) -> Tuple[Tensor, Tensor]:
+    """(high, low) 32-bit halves of a * b for a 32-bit constant and an int64 tensor of 32-bit values,
+    through 16-bit halves of b so that nothing passes 2^63."""
+    p0, p1 = a * (b & 0xFFFF), a * (b >> 16)
+    low = p0 + ((p1 & 0xFFFF) << 16)
+    return (p1 >> 16) + (low >> 32), low & _M32
+
+
+def philox4x32_10(counter: Tensor, key: Tensor) -> Tensor:
+    """Philox4x32-10 in integer tensor ops: counter (..., 4) and key (..., 2), int64 tensors holding
+    32-bit words; returns the four output words (..., 4)."""
+    c0, c1, c2, c3 = (counter[..., i] & _M32 for i in range(4))
+    k0, k1 = key[..., 0] & _M32, key[..., 1] & _M32
+    for _ in range(10):
+        h0, l0 = _mulhilo32(_PHILOX_M0, c0)
+        h1, l1 = _mulhilo32(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return torch.stack((c0, c1, c2, c3), dim=-1)
+
+
+def sample_uniform(seed: int, stream: Tensor, offset: Tensor) -> Tensor:
+    """The sampler's uniform, fp64 in [0, 1): ``(out[0] >> 8) * 2^-24`` of Philox4x32-10 with key
+    (seed lo, seed hi) and counter (offset lo, offset hi, stream lo, stream hi); stream and offset are
+    int64 tensors of one shape (read as unsigned 64-bit)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    halves = lambda t: (t & _M32, (t >> 32) & _M32)                    # noqa: E731
+    counter = torch.stack(halves(offset) + halves(stream), dim=-1)
+    key = torch.tensor([seed & _M32, seed >> 32], dtype=torch.int64, device=stream.device).expand(*stream.shape, 2)
+    return (philox4x32_10(counter, key)[..., 0] >> 8).double() * 2.0 ** -24
+
+
+def _sample_rows_2d(logits: Tensor) -> Tensor:
+    if not isinstance(logits, Tensor) or logits.dim() < 1 or logits.shape[-1] < 1:
+        raise RuntimeError("logits must be (..., V) with V >= 1")
+    if logits.dtype not in _lib._DTYPES:
+        raise RuntimeError(f"logits must be bf16, fp16 or fp32, got {logits.dtype}")
+    if logits.shape[-1] > SAMPLE_MAX_V:
+        raise RuntimeError(f"V {logits.shape[-1]} is above {SAMPLE_MAX_V}")
+    x = logits if logits.dim() == 2 else logits.reshape(-1, logits.shape[-1])
+    return x if x.stride(1) == 1 or x.shape[1] == 1 else x.contiguous()
+
+
+def _sample_param(v, R: int, dtype, device, name: str):
+    """A sampling parameter as (scalar, per-row tensor or None)."""
+    if isinstance(v, Tensor):
+        if v.numel() != R or v.device != device:
+            raise RuntimeError(f"{name} must be a scalar or a tensor of {R} entries on {device}")
+        return None, v.reshape(R).to(dtype).contiguous()
+    v = float(v) if dtype.is_floating_point else int(v)
+    if v != v:
+        raise RuntimeError(f"{name} is NaN")
+    return v, None
+
+
+def _sample_counter(v, R: int, device, name: str) -> Optional[Tensor]:
+    if v is None:
+        return None
+    if not isinstance(v, Tensor):
+        return torch.full((R,), int(v), dtype=torch.int64, device=device)
+    if v.numel() != R or v.device != device or v.dtype != torch.int64:
+        raise RuntimeError(f"{name} must be an int64 tensor of {R} entries on {device}")
+    return v.reshape(R).contiguous()
+
+
+def sample_rows_reference(logits: Tensor, temperature=1.0, top_k=0, top_p=1.0, seed: int = 0, stream=None,
+                          offset=None, return_logprobs: bool = False, kept_only: bool = False):
+    """``sample_rows`` in torch, on the logits' device: the same definition with fp64 weights and
+    sums (so a token may differ from the kernel's where ``u * Z`` falls within rounding of a CDF
+    step).  The tests' oracle, and what ``sample_rows`` runs on CPU tensors and on a library without
+    ``dta_sample_rows``.  ``kept_only``: return instead the bool mask, shaped like ``logits``, of what
+    top-k and top-p keep (all False for a greedy or a degenerate row)."""
+    x2 = _sample_rows_2d(logits)
+    R, V = x2.shape
+    dev = x2.device
+    as_rows = lambda s, t, dt: t.to(dt) if t is not None else torch.full((R,), s, dtype=dt, device=dev)   # noqa: E731
+    T = as_rows(*_sample_param(temperature, R, torch.float32, dev, "temperature"), torch.float32).double()
+    k = as_rows(*_sample_param(top_k, R, torch.int32, dev, "top_k"), torch.int64)
+    p = as_rows(*_sample_param(top_p, R, torch.float32, dev, "top_p"), torch.float32).double()
+    strm = _sample_counter(stream, R, dev, "stream")
+    strm = torch.arange(R, dtype=torch.int64, device=dev) if strm is None else strm
+    off = _sample_counter(offset, R, dev, "offset")
+    off = torch.zeros(R, dtype=torch.int64, device=dev) if off is None else off
+    x = x2.float().double()
+    ninf = float("-inf")
+    bad = torch.isnan(x).any(1) | (x == float("inf")).any(1) | (x == ninf).all(1)
+    x = torch.where(bad[:, None], torch.zeros_like(x), x)              # any finite row: the result is overwritten
+    cols = torch.arange(V, device=dev)
+    m = x.max(dim=1, keepdim=True).values
+    amax = torch.where(x == m, cols, V).min(dim=1).values
+    greedy = torch.isnan(T) | (T <= 0)
+    T = torch.where(greedy, torch.ones_like(T), T)
+    z = (x - m) / T[:, None]
+    w = torch.exp(z)
+    # top-k: the k-th largest value and everything that ties with it
+    xs, order = torch.sort(x, dim=1, descending=True, stable=True)
+    k_on = (k > 0) & (k < V)
+    kth = xs.gather(1, (torch.where(k_on, k, V) - 1)[:, None])
+    kept = x >= kth
+    # top-p among those: G_i = the kept weight strictly above x_i, taken at the head of its tie class
+    ws = torch.where(kept, w, torch.zeros_like(w)).gather(1, order)
+    above = ws.cumsum(1) - ws
+    head = torch.ones_like(xs, dtype=torch.bool)
+    head[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    G = torch.where(head, above, torch.zeros_like(above)).cummax(dim=1).values
+    Zk = ws.sum(1, keepdim=True)
+    p_on = (p > 0) & (p < 1)
+    in_p = torch.zeros_like(kept).scatter(1, order, G < p[:, None] * Zk)
+    kept = kept & (in_p | ~p_on[:, None])
+    if kept_only:
+        return (kept & ~greedy[:, None] & ~bad[:, None]).reshape(logits.shape)
+    wk = torch.where(kept, w, torch.zeros_like(w))
+    Z = wk.sum(1)
+    C = wk.cumsum(1)
+    u = sample_uniform(seed, strm, off)
+    hit = kept & (C > (u * Z)[:, None])
+    tok = torch.where(hit, cols, V).min(dim=1).values
+    last = torch.where(kept, cols, -1).max(dim=1).values
+    tok = torch.where(tok == V, last, tok)
+    lp = z.gather(1, tok[:, None])[:, 0] - torch.log(Z)
+    lp_greedy = -torch.log(w.sum(1))
+    tok = torch.where(greedy, amax, tok)
+    lp = torch.where(greedy, lp_greedy, lp)
+    tok = torch.where(bad, torch.full_like(tok, -1), tok).reshape(logits.shape[:-1])
+    if not return_logprobs:
+        return tok
+    lp = torch.where(bad, torch.full_like(lp, float("nan")), lp).float()
+    return tok, lp.reshape(logits.shape[:-1])
+
+
+def sample_rows(logits: Tensor, temperature=1.0, top_k=0, top_p=1.0, seed: int = 0, stream=None, offset=None,
+                return_logprobs: bool = False):
+    """One sampled token per row of ``logits`` (R, V) -- or (..., V), flattened -- in one launch
+    (``dta_sample_rows``): temperature (``<= 0``: greedy), top-k (``<= 0`` or ``>= V``: off) and top-p
+    (``>= 1`` or ``<= 0``: off), each a scalar or a device tensor of R entries, and a uniform drawn by
+    Philox4x32-10 from ``(seed, stream[r], offset[r])`` (int64 tensors; default the row index and 0).
+    A row's result is a bitwise function of the row, its parameters and that triple: the same in any
+    batch, at any row index, from an eager call or a graph replay.
+
+    Returns int64 tokens shaped like ``logits`` without its last dimension, -1 for a row that holds
+    a NaN or +inf or is all -inf; with ``return_logprobs`` also the fp32 log-probability of each
+    token under the filtered, tempered distribution (greedy: under the plain softmax).
+
+    bf16, fp16 or fp32 logits, any row stride, ``1 <= V <= 2^20``.  CPU tensors, and a library
+    without the entry point, run ``sample_rows_reference``."""
+    x2 = _sample_rows_2d(logits)
+    if x2.device.type != "cuda" or not sample_supported():
+        return sample_rows_reference(logits, temperature, top_k, top_p, seed, stream, offset, return_logprobs)
+    R, V = x2.shape
+    dev = x2.device
+    T, T_dev = _sample_param(temperature, R, torch.float32, dev, "temperature")
+    k, k_dev = _sample_param(top_k, R, torch.int32, dev, "top_k")
+    p, p_dev = _sample_param(top_p, R, torch.float32, dev, "top_p")
+    strm = _sample_counter(stream, R, dev, "stream")
+    off = _sample_counter(offset, R, dev, "offset")
+    tokens = torch.empty(R, device=dev, dtype=torch.int64)
+    logprobs = torch.empty(R, device=dev, dtype=torch.float32) if return_logprobs else None
+    if R > 0:
+        k = max(min(k, 2 ** 31 - 1), 0) if k is not None else 0
+        a = _lib.SampleRowsArgs(_lib.dtype_code(x2.dtype), R, V, x2.data_ptr(), x2.stride(0),
+                                1.0 if T is None else T, k, 1.0 if p is None else p,
+                                _lib.ptr(T_dev), _lib.ptr(k_dev), _lib.ptr(p_dev), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                _lib.ptr(strm), _lib.ptr(off), tokens.data_ptr(), _lib.ptr(logprobs))
+        _lib.check(_lib.load().dta_sample_rows(a, _lib.stream_handle(dev)))
+    tokens = tokens.reshape(logits.shape[:-1])
+    return (tokens, logprobs.reshape(logits.shape[:-1])) if return_logprobs else tokens
+
+
 # ------------------------------------------------------ shared-prefix decode ---
 # The one-row paged decode for a batch in which groups of sequences have the same pool pages under
 # their first rows (``PagedKVCache.fork``, ``generate_paged(n_samples=k)``): a group pass reads the

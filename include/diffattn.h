@@ -73,6 +73,8 @@ extern "C" {
                                   (e4m3fn pages with per-(row, head) scales);
                                   still 9, added the same way: dta_kv_step_rows (a step's RoPE and cache
                                   scatter in one launch);
+                                  still 9, added the same way: dta_sample_rows (seeded temperature /
+                                  top-k / top-p sampling, one token per logits row);
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -809,6 +811,51 @@ typedef struct dta_kv_step_rows_args {
   int32_t* slots_out_dev;    /* device int32 [B * Tn]; slots */
 } dta_kv_step_rows_args;
 int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream);
+
+/* Sampling: one token per logits row, in one launch (one 256-thread workgroup per row).  Replaces
+ * softmax + multinomial of the generate loops where a sampler is asked for.  For row r, with
+ * x_i = float(logits[r][i]) over V columns, T = temperature, k = top_k, p = top_p (the per-row
+ * device value where the pointer is set, the scalar otherwise):
+ *   degenerate   a row holding a NaN or a +inf, or all -inf: token -1, logprob NaN.  Every other row
+ *                gives 0 <= token < V; nothing outside [-1, V) is ever written.
+ *   m = max x_i.  T <= 0 (or a NaN device T): greedy, the lowest index with x_i == m, and
+ *                logprob = x_t - m - log sum_i exp(x_i - m) (temperature 1, unfiltered).
+ *   weights      z_i = (x_i - m) / T, w_i = exp(z_i), fp32
+ *   top-k        off if k <= 0 or k >= V; i is kept iff #{j : x_j > x_i} < k (a tie class at the
+ *                threshold is kept whole)
+ *   top-p        off if p >= 1 or p <= 0 (or a NaN device p); among what top-k kept, i is kept iff
+ *                sum_{j kept by k, x_j > x_i} w_j < p * sum_{j kept by k} w_j (the maximum always is;
+ *                ties in or out together)
+ *   draw         Z = sum of the kept w_i; the token is the lowest kept index whose inclusive prefix
+ *                sum of kept weights, in index order, exceeds u * Z (the last kept index if rounding
+ *                leaves none); logprob = z_t - log Z
+ *   u            Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (offset lo, offset hi,
+ *                stream lo, stream hi); u = (out[0] >> 8) * 2^-24.  No generator state, no host call.
+ * A row's token and logprob are a bitwise function of the row, its parameters and (seed, stream,
+ * offset): independent of R, of the row's index, of alignment and of timing (fixed-shape sums, no
+ * floating-point atomics).  Any V in [1, 2^20], any row stride (elements); 16-byte loads where a
+ * row starts 16-byte aligned, element loads otherwise.
+ * DTA_ERR_INVALID: a null logits / token_out with R > 0, R < 0, V < 1, an unknown dtype, a NaN scalar
+ * temperature / top_p, a per-row pointer not aligned to its element (4 bytes fp32 / int32, 8 bytes
+ * int64).  DTA_ERR_UNSUPPORTED: V > 2^20.  R == 0: DTA_OK, no launch. */
+typedef struct dta_sample_rows_args {
+  int32_t dtype;
+  int32_t R, V;
+  const void* logits;
+  int64_t row_stride;                /* elements */
+  float temperature;                 /* the scalars: used where the per-row pointer is NULL */
+  int32_t top_k;
+  float top_p;
+  const float* temperature_dev;      /* device [R], or NULL */
+  const int32_t* top_k_dev;
+  const float* top_p_dev;
+  uint64_t seed;
+  const int64_t* stream_dev;         /* device [R], or NULL: stream = row index */
+  const int64_t* offset_dev;         /* device [R], or NULL: offset = 0 */
+  int64_t* token_out;                /* device [R] */
+  float* logprob_out;                /* device [R], or NULL */
+} dta_sample_rows_args;
+int dta_sample_rows(const dta_sample_rows_args* a, void* stream);
 
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
