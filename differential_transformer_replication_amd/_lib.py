@@ -44,7 +44,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # the fused row write of a ragged / paged step, added the same way
            "dta_kv_step_rows",
            # seeded temperature / top-k / top-p sampling of logits rows, added the same way
-           "dta_sample_rows")
+           "dta_sample_rows",
+           # a speculative round's acceptance and next prompt-lookup draft, added the same way
+           "dta_spec_accept_draft")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
@@ -59,6 +61,8 @@ SHARED_EXPORTS = ("dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_
 STEP_EXPORTS = ("dta_kv_step_rows",)
 # and the row sampler (``ops.sample_supported``), added the same way
 SAMPLE_EXPORTS = ("dta_sample_rows",)
+# and the speculative round's accept + draft kernel (``ops.spec_supported``), added the same way
+SPEC_EXPORTS = ("dta_spec_accept_draft",)
 
 
 class DtaTensor(ctypes.Structure):
@@ -229,6 +233,13 @@ class SampleRowsArgs(ctypes.Structure):
                 ("token_out", ctypes.c_void_p), ("logprob_out", ctypes.c_void_p)]
 
 
+class SpecAcceptDraftArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("B", "Tn", "K", "cap", "t_cap", "ngram_min", "ngram_max", "eos_id")]
+                + [(n, ctypes.c_int64) for n in ("hist_stride", "draft_stride", "tok_stride")]
+                + [(n, ctypes.c_void_p) for n in ("hist", "hlen_dev", "remaining_dev", "draft", "dcnt_dev", "tok",
+                                                  "result_out")])
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -310,6 +321,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if sample_symbols(lib):
             lib.dta_sample_rows.argtypes = [P(SampleRowsArgs), ctypes.c_void_p]
             lib.dta_sample_rows.restype = ctypes.c_int
+        if spec_symbols(lib):
+            lib.dta_spec_accept_draft.argtypes = [P(SpecAcceptDraftArgs), ctypes.c_void_p]
+            lib.dta_spec_accept_draft.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -348,6 +362,12 @@ def step_symbols(lib) -> bool:
 def sample_symbols(lib) -> bool:
     """Whether ``lib`` exports the row sampler (it arrived inside ABI 9, after the fused row write)."""
     return all(hasattr(lib, name) for name in SAMPLE_EXPORTS)
+
+
+def spec_symbols(lib) -> bool:
+    """Whether ``lib`` exports the speculative round's accept + draft kernel (it arrived inside ABI 9, after
+    the row sampler)."""
+    return all(hasattr(lib, name) for name in SPEC_EXPORTS)
 
 
 def check(rc: int) -> None:

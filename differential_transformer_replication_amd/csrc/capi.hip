@@ -774,6 +774,27 @@ int dta_sample_rows(const dta_sample_rows_args* a, void* stream) {
   return status(launch_sample(a->dtype, p, (hipStream_t)stream));
 }
 
+int dta_spec_accept_draft(const dta_spec_accept_draft_args* a, void* stream) {
+  if (!a || a->B < 0 || a->K < 1 || a->K > 7 || a->Tn < 0 || a->Tn > a->K + 1) return DTA_ERR_INVALID;
+  if (a->ngram_min < 0 || a->ngram_min > a->ngram_max || a->ngram_max < 1 || a->ngram_max > 8) return DTA_ERR_INVALID;
+  if (a->cap < 1 || a->cap > (1 << 30) || a->t_cap < 1 || a->t_cap > (1 << 30)) return DTA_ERR_INVALID;
+  if (a->hist_stride < a->cap || a->draft_stride < a->K || a->tok_stride < a->Tn) return DTA_ERR_INVALID;
+  if (!a->hist || !a->hlen_dev || !a->remaining_dev || !a->draft || !a->dcnt_dev || !a->result_out ||
+      (a->Tn > 0 && !a->tok))
+    return DTA_ERR_INVALID;
+  if ((uintptr_t)a->hist % 4 || (uintptr_t)a->hlen_dev % 4 || (uintptr_t)a->remaining_dev % 4 || (uintptr_t)a->draft % 4 ||
+      (uintptr_t)a->dcnt_dev % 4 || (uintptr_t)a->result_out % 4 || (uintptr_t)a->tok % 8)
+    return DTA_ERR_INVALID;
+  if (a->B == 0) return DTA_OK;
+  SpecParams p{};
+  p.hist = a->hist; p.hlen = a->hlen_dev; p.remaining = a->remaining_dev; p.draft = a->draft; p.dcnt = a->dcnt_dev;
+  p.tok = a->tok; p.result = a->result_out;
+  p.hist_stride = a->hist_stride; p.draft_stride = a->draft_stride; p.tok_stride = a->tok_stride;
+  p.B = a->B; p.Tn = a->Tn; p.K = a->K; p.cap = a->cap; p.t_cap = a->t_cap;
+  p.nmin = a->ngram_min; p.nmax = a->ngram_max; p.eos = a->eos_id;
+  return status(launch_spec(p, (hipStream_t)stream));
+}
+
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }

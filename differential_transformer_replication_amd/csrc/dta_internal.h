@@ -203,6 +203,20 @@ struct SampleParams {
 };
 int launch_sample(int dtype, const SampleParams& p, hipStream_t st);
 
+// dta_spec_accept_draft (spec.hip): a speculative round's acceptance, history append and next n-gram draft
+struct SpecParams {
+  int* hist;           // [B][cap], row stride in elements
+  int* hlen;           // [B], clamped to [0, cap]
+  int* remaining;      // [B]; <= 0: a finished row
+  int* draft;          // [B][K]
+  int* dcnt;           // [B], clamped to [0, min(K, Tn - 1)]
+  const int64_t* tok;  // [B][Tn]
+  int* result;         // [B][2]: (m, next dcnt)
+  int64_t hist_stride, draft_stride, tok_stride;
+  int B, Tn, K, cap, t_cap, nmin, nmax, eos;   // nmin 0: no lookup, the next dcnt is 0
+};
+int launch_spec(const SpecParams& p, hipStream_t st);
+
 struct ExtendParams {
   T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid
   const float* coef;   // [h][i]

@@ -50,6 +50,11 @@ rows are one ``ops.kv_step_rows`` launch (``step_rows``).
 Every generate loop takes ``sampler=None``: a ``Sampler`` (temperature, top-k, top-p, seed) replaces the
 reference's two sampling lines by one ``ops.sample_rows`` launch per step whose draw for a sequence depends
 on (seed, the sequence's stream, its position) only; None keeps the reference's lines, token for token.
+
+``generate_ragged`` / ``generate_paged`` also take ``speculate=None``: a ``Speculation`` makes every model step
+a round that scores the pending token and up to k drafted ones (``append_*(all_rows=True)``), samples every
+row with the offsets the plain loop would use, and lets ``ops.spec_accept_draft`` accept, append and draft
+again on the device (``_speculative_tokens``).  The tokens are the ``sampler`` loop's, token for token.
 """
 from __future__ import annotations
 
@@ -65,7 +70,7 @@ from ._compat import mha_out_scale
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
            "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
-           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler"]
+           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler", "Speculation"]
 
 
 class Sampler:
@@ -98,6 +103,40 @@ class Sampler:
         out = ops.sample_rows(logits, self.temperature, self.top_k, self.top_p, self.seed, streams, offset,
                               return_logprobs)
         return (out[0][:, None], out[1]) if return_logprobs else out[:, None]
+
+
+class Speculation:
+    """Opt-in speculative decoding of ``generate_ragged`` / ``generate_paged`` by prompt lookup: each round
+    verifies up to ``k`` (1 .. 7) drafted tokens in one multi-row step.  The draft is the continuation of the
+    longest (``ngram_max`` .. ``ngram_min`` tokens, at most 8), then latest, earlier occurrence of the
+    sequence's last tokens in its own history; it is deterministic, so accepting a draft iff it equals the
+    token sampled at its position -- with the uniform the plain loop would draw there -- emits exactly the
+    plain ``sampler`` loop's tokens, whatever is drafted.  ``drafter``: an object whose
+    ``propose(hist, hlen, remaining, k) -> (draft, dcnt)`` replaces the lookup (device tensors: int32
+    (B, cap) histories, their lengths, the tokens still owed; returns an integer (B, k) draft and its (B,)
+    lengths, which the loop clips to what the window and ``remaining`` allow).  Immutable; ``stats`` holds
+    the counts of the last call: ``rounds`` (model steps), ``drafted`` and ``accepted`` draft tokens,
+    ``emitted`` tokens."""
+    __slots__ = ("k", "ngram_max", "ngram_min", "drafter", "stats")
+
+    def __init__(self, k: int = 4, ngram_max: int = 3, ngram_min: int = 1, drafter=None):
+        k, ngram_max, ngram_min = int(k), int(ngram_max), int(ngram_min)
+        if not 1 <= k <= ops.SPEC_MAX_K:
+            raise ValueError(f"k {k} outside 1 .. {ops.SPEC_MAX_K}")
+        if not 1 <= ngram_min <= ngram_max <= ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"need 1 <= ngram_min {ngram_min} <= ngram_max {ngram_max} <= {ops.SPEC_MAX_NGRAM}")
+        if drafter is not None and not callable(getattr(drafter, "propose", None)):
+            raise ValueError("drafter must have propose(hist, hlen, remaining, k) -> (draft, dcnt)")
+        for name, v in (("k", k), ("ngram_max", ngram_max), ("ngram_min", ngram_min), ("drafter", drafter),
+                        ("stats", dict(rounds=0, drafted=0, accepted=0, emitted=0))):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Speculation is immutable")
+
+    def __repr__(self):
+        return (f"Speculation(k={self.k}, ngram_max={self.ngram_max}, ngram_min={self.ngram_min}, "
+                f"drafter={self.drafter!r})")
 
 
 def _stream_ids(streams, B: int, n_samples: int, device) -> Optional[torch.Tensor]:
@@ -803,6 +842,89 @@ def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode, s
     return toks, keep
 
 
+def _check_speculate(speculate, sampler, n_samples: int = 1, shared_decode: bool = False) -> None:
+    if not isinstance(speculate, Speculation):
+        raise ValueError("speculate must be a Speculation")
+    if sampler is None:
+        raise ValueError("speculate needs a sampler: the reference's batch-wide torch.multinomial has no "
+                         "per-sequence stream to couple the verification to")
+    if n_samples > 1:
+        raise ValueError("speculate with n_samples > 1 is not supported")
+    if shared_decode:
+        raise ValueError("speculate with shared_decode=True is not supported")
+
+
+def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[int], sampler: Sampler,
+                        streams: Optional[torch.Tensor], spec: Speculation, bs: int, append, truncate):
+    """``_sample_tokens`` by speculative rounds, for ``max_new_tokens >= 1``.  ``logits`` (B, vocab) are the
+    prefill's; ``append(new_idx, counts)`` is the cache's multi-row step with ``all_rows=True`` and
+    ``truncate(lengths)`` its roll-back.  Per sequence the device holds the token history (prompt and
+    emitted tokens; the last one is pending: emitted, not yet through the model), the tokens still owed
+    and the draft.  A round feeds [pending, draft...] (counts ``dcnt + 1``, 0 for a finished sequence),
+    samples every row in one ``ops.sample_rows`` launch -- sequence b's row j with (stream b, offset =
+    tokens emitted so far + j), the plain loop's -- runs one ``ops.spec_accept_draft`` and reads one
+    small tensor back ((m, next dcnt) and the tokens still owed), then truncates each cache to its old
+    length + m.  The first token comes from the prefill's logits through the same kernel, with no draft
+    to accept.  Returns the histories: a list of B int64 tensors, prompt included."""
+    dev = logits.device
+    B, K = len(prompts), spec.k
+    lens = [int(p.shape[0]) for p in prompts]
+    cap = max(lens) + max_new_tokens
+    hist = torch.zeros(B, cap, dtype=torch.int32, device=dev)
+    hist[:, :max(lens)] = torch.nn.utils.rnn.pad_sequence(list(prompts), batch_first=True).to(dev, torch.int32)
+    hlen = torch.tensor(lens, dtype=torch.int32, device=dev)
+    draft = torch.zeros(B, K, dtype=torch.int32, device=dev)
+    dcnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    back = torch.zeros(3 * B, dtype=torch.int32, device=dev)     # (m, next dcnt) next to the tokens still owed:
+    result, remaining = back[:2 * B].view(B, 2), back[2 * B:]    # one read a round
+    remaining.fill_(max_new_tokens)
+    strm = torch.arange(B, dtype=torch.int64, device=dev) if streams is None else streams
+    eos = -1 if eos_id is None else int(eos_id)
+    lookup = spec.drafter is None
+    stats = spec.stats
+    stats.update(rounds=0, drafted=0, accepted=0, emitted=0)
+
+    def accept(tok):
+        ops.spec_accept_draft(hist, hlen, remaining, draft, dcnt, tok, eos, K, spec.ngram_min if lookup else 0,
+                              spec.ngram_max, bs, result)
+        if not lookup:
+            d, n = spec.drafter.propose(hist, hlen, remaining, K)
+            room = torch.minimum(remaining - 1, bs - hlen).clamp(0, K)
+            dcnt.copy_(torch.minimum(n.to(dev, torch.int32), room))
+            draft.copy_(d.to(dev, torch.int32))
+            result[:, 1] = dcnt
+        host = back.tolist()
+        return host[0:2 * B:2], host[1:2 * B:2], host[2 * B:]
+
+    have = list(lens)                                            # rows in the cache
+    tok = sampler.sample(logits, 0, strm)                        # (B, 1): offset 0 of every stream
+    m, dc, rem = accept(tok)
+    stats["emitted"] += sum(m)
+    cols = torch.arange(K, device=dev)
+    while any(r > 0 for r in rem):
+        counts = [d + 1 if r > 0 else 0 for d, r in zip(dc, rem)]
+        Tn = max(counts)
+        pending = hist.gather(1, (hlen.long() - 1).clamp_(min=0)[:, None])
+        drafted = torch.where(cols[None, :Tn - 1] < dcnt[:, None], draft[:, :Tn - 1], 0)
+        new_idx = torch.cat([pending, drafted], dim=1).long().clamp_(min=0)
+        rows = append(new_idx, counts)                           # (B, Tn, vocab)
+        offset = (max_new_tokens - remaining.long())[:, None] + torch.arange(Tn, device=dev)[None, :]
+        tok = ops.sample_rows(rows, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed,
+                              strm[:, None].expand(B, Tn).reshape(-1), offset.reshape(-1))
+        m, dc_next, rem = accept(tok)
+        have = [n + k for n, k in zip(have, m)]
+        if any(k < c for k, c in zip(m, counts)):
+            truncate(have)
+        stats["rounds"] += 1
+        stats["drafted"] += sum(c - 1 for c in counts if c)
+        stats["accepted"] += sum(k - 1 for k in m if k)
+        stats["emitted"] += sum(m)
+        dc = dc_next
+    ends = hlen.tolist()
+    out = hist.cpu()
+    return [out[b, :ends[b]].long() for b in range(B)]
+
+
 def _check_ragged(cache, B: int) -> None:
     if not isinstance(cache, RaggedKVCache) or cache.lengths is None:
         raise ValueError("a prefilled RaggedKVCache is needed: run prefill_ragged first")
@@ -893,7 +1015,7 @@ def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, al
 @torch.no_grad()
 def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
                     graph: bool = False, fused_step: bool = False, sampler: Optional[Sampler] = None,
-                    streams: Optional[Sequence[int]] = None):
+                    streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None):
     """``generate`` for B prompts of different lengths as one batch (any of the three
     models): one ``prefill_ragged``, then one ``decode_ragged`` step per token.  Sampling
     is the reference's (softmax of the last logits, ``torch.multinomial`` over the whole
@@ -911,16 +1033,30 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     ``sampler``: a ``Sampler`` replaces softmax + multinomial by one ``ops.sample_rows`` launch per step,
     run eagerly after the step or its graph replay; sequence b's t-th token is drawn from (seed,
     stream b, offset t) -- ``streams`` gives the prompts other stream ids -- so it does not depend on
-    the rest of the batch.  None (the default): the reference's sampling, token for token."""
+    the rest of the batch.  None (the default): the reference's sampling, token for token.
+    ``speculate``: a ``Speculation`` (needs a ``sampler``) runs the loop as speculative rounds
+    (``_speculative_tokens``): the same tokens as without it, token for token, in fewer model steps where the
+    drafts are accepted.  The cache is then made with ``rows_decode=True``, so a round of 2 .. 8 rows that
+    has a plan reads the cache once and every row is the one-row decode's; ``graph`` / ``fused_step`` keep
+    their meaning for one-token steps and rounds do not use the graph; a round reads three small integers
+    per sequence back."""
     bs = model.block_size
+    if speculate is not None:
+        _check_speculate(speculate, sampler)
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
                              f"block_size {bs}: the sliding window is the one-length path's job")
-    cache = RaggedKVCache(graph=graph, fused_step=fused_step)
+    cache = RaggedKVCache(rows_decode=speculate is not None, graph=graph, fused_step=fused_step)
     logits = prefill_ragged(model, prompts, cache)
     if max_new_tokens < 1:
         return [p.clone() for p in prompts]
+    if speculate is not None:
+        outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
+                                   _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
+                                   lambda idx, counts: append_ragged(model, idx, counts, cache, all_rows=True),
+                                   cache.truncate)
+        return [o.to(p.device) for o, p in zip(outs, prompts)]
     toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
                                 lambda tok, active: decode_ragged(model, tok, cache, active), sampler,
                                 _stream_ids(streams, len(prompts), 1, logits.device))
@@ -1437,7 +1573,7 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
                    n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
                    rows_decode: bool = False, shared_decode: bool = False, graph: bool = False,
                    fused_step: bool = False, sampler: Optional[Sampler] = None,
-                   streams: Optional[Sequence[int]] = None):
+                   streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1455,10 +1591,15 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     ``graph`` / ``fused_step``: ``PagedKVCache``'s (each token's step replays one captured HIP graph; its
     RoPE and row scatter are one launch; not with ``shared_decode``): same logits, bit for bit.
     ``sampler`` / ``streams``: ``generate_ragged``'s; sample j of prompt b draws from stream
-    ``b * n_samples + j`` (``streams[b] * n_samples + j``), so the forks of one prompt differ."""
+    ``b * n_samples + j`` (``streams[b] * n_samples + j``), so the forks of one prompt differ.
+    ``speculate``: ``generate_ragged``'s (not with ``n_samples > 1`` or ``shared_decode``); the pool is made
+    with ``rows_decode=True``, a round takes pages for its drafted rows and ``truncate`` returns those of
+    the rejected ones, so the default ``num_pages`` still holds the call."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
+    if speculate is not None:
+        _check_speculate(speculate, sampler, n_samples, shared_decode)
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
@@ -1471,8 +1612,20 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
             num_pages += shared + n_samples * (-(-end // page_size) - shared)
         num_pages = max(num_pages, 1)
     cache = PagedKVCache(num_pages, page_size, max_seqs=max(len(prompts) * n_samples, 1), kv_dtype=kv_dtype,
-                          rows_decode=rows_decode, shared_decode=shared_decode, graph=graph, fused_step=fused_step)
+                          rows_decode=rows_decode or speculate is not None, shared_decode=shared_decode, graph=graph,
+                          fused_step=fused_step)
     roots, logits = prefill_paged(model, prompts, cache)
+    if speculate is not None and max_new_tokens >= 1:
+        def roll_back(lengths):
+            for q, n in zip(roots, lengths):
+                if n < cache.host_lengths[q]:
+                    cache.truncate(q, n)
+
+        outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
+                                   _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
+                                   lambda idx, counts: append_paged(model, roots, idx, counts, cache, all_rows=True),
+                                   roll_back)
+        return [o.to(p.device) for o, p in zip(outs, prompts)]
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]
     if max_new_tokens >= 1:

@@ -1523,6 +1523,141 @@ def sample_rows(logits: Tensor, temperature=1.0, top_k=0, top_p=1.0, seed: int =
     return (tokens, logprobs.reshape(logits.shape[:-1])) if return_logprobs else tokens
 
 
+# ------------------------------------------------------ speculative decoding ---
+# One round of prompt-lookup speculative decoding on the device: which of the round's sampled rows are
+# emitted, the append to the sequence's history and the next draft by n-gram lookup.  The definition is
+# include/diffattn.h's ("Speculative decoding"); ``spec_accept_draft`` is the HIP kernel,
+# ``spec_accept_draft_reference`` the same definition in torch.  Both update the state in place.
+SPEC_MAX_K = 7
+SPEC_MAX_NGRAM = 8
+
+
+def spec_supported() -> bool:
+    """Whether the loaded library has ``dta_spec_accept_draft`` (an older build of the same ABI may not)."""
+    return _lib.spec_symbols(_lib.load())
+
+
+def _spec_check(hist, hlen, remaining, draft, dcnt, tok, result, k, ngram_min, ngram_max, t_cap):
+    """The shapes and values both implementations insist on; returns (B, cap, Tn, tok as (B, Tn) or None)."""
+    k, ngram_min, ngram_max, t_cap = int(k), int(ngram_min), int(ngram_max), int(t_cap)
+    if not 1 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k {k} outside 1 .. {SPEC_MAX_K}")
+    if not (0 <= ngram_min <= ngram_max and 1 <= ngram_max <= SPEC_MAX_NGRAM):
+        raise ValueError(f"need 0 <= ngram_min {ngram_min} <= ngram_max {ngram_max}, 1 <= ngram_max <= {SPEC_MAX_NGRAM}")
+    if hist.dim() != 2 or hist.shape[1] < 1 or t_cap < 1:
+        raise ValueError("hist must be (B, cap) with cap >= 1, and t_cap >= 1")
+    B, cap = hist.shape
+    Tn = 0
+    if tok is not None:
+        if tok.dim() != 2 or tok.shape[0] != B or tok.dtype != torch.int64 or tok.device != hist.device:
+            raise ValueError(f"tok must be an int64 (B, Tn) tensor on {hist.device}")
+        Tn = tok.shape[1]
+        if Tn > k + 1:
+            raise ValueError(f"tok has {Tn} columns, a round has at most k + 1 = {k + 1} rows")
+    for name, t, shape in (("hist", hist, (B, cap)), ("hlen", hlen, (B,)), ("remaining", remaining, (B,)),
+                           ("draft", draft, (B, k)), ("dcnt", dcnt, (B,)), ("result", result, (B, 2))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != hist.device:
+            raise ValueError(f"{name} must be an int32 {shape} tensor on {hist.device}")
+        if (t.stride(-1) != 1 and t.shape[-1] > 1) or (t.dim() == 2 and B > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{name} must have contiguous rows that do not overlap: it is updated in place")
+    for name, t in (("hlen", hlen), ("remaining", remaining), ("dcnt", dcnt), ("result", result)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return B, cap, Tn
+
+
+def spec_accept_draft_reference(hist: Tensor, hlen: Tensor, remaining: Tensor, draft: Tensor, dcnt: Tensor,
+                                tok: Optional[Tensor], eos_id: int = -1, k: int = 4, ngram_min: int = 1,
+                                ngram_max: int = 3, t_cap: int = 1 << 30, result: Optional[Tensor] = None) -> Tensor:
+    """``spec_accept_draft`` in torch and Python, on the tensors' device: include/diffattn.h's definition
+    a row at a time, the lookup vectorised over the ends.  The tests' oracle, and what
+    ``spec_accept_draft`` runs on CPU tensors and on a library without the entry point."""
+    if result is None:
+        result = torch.zeros(hist.shape[0], 2, dtype=torch.int32, device=hist.device)
+    B, cap, Tn = _spec_check(hist, hlen, remaining, draft, dcnt, tok, result, k, ngram_min, ngram_max, t_cap)
+    k, ngram_min, ngram_max, t_cap, eos_id = int(k), int(ngram_min), int(ngram_max), int(t_cap), int(eos_id)
+    lens, rems, dcs = hlen.tolist(), remaining.tolist(), dcnt.tolist()
+    toks = tok.tolist() if Tn else [[] for _ in range(B)]
+    for b in range(B):
+        rem = rems[b]
+        if rem <= 0:
+            result[b, 0], result[b, 1] = 0, 0
+            continue
+        L0 = min(max(lens[b], 0), cap)
+        dc = min(max(dcs[b], 0), min(k, max(Tn - 1, 0)))
+        t, d = toks[b], draft[b, :dc].tolist()
+        a = 0
+        while a < dc and t[a] == d[a]:
+            a += 1
+        m = min(a + 1, rem, Tn, cap - L0)
+        stop = False
+        for j in range(m):
+            if t[j] < 0 or t[j] == eos_id:
+                m, stop = j + 1, True
+                break
+        rem = 0 if stop else rem - m
+        if m:
+            hist[b, L0:L0 + m] = torch.tensor(t[:m], dtype=torch.int64, device=hist.device).to(torch.int32)
+        L = L0 + m
+        nd = 0
+        if ngram_min >= 1 and rem > 1 and L > ngram_min:
+            h = hist[b, :L].long()
+            e = torch.arange(ngram_min - 1, L - 1, device=h.device)
+            same = torch.ones_like(e, dtype=torch.bool)
+            mu = torch.zeros_like(e)
+            for n in range(min(ngram_max, L - 1)):               # mu(e) <= e + 1 <= L - 1
+                ok = e - n >= 0
+                same = same & ok & (h[(e - n).clamp(min=0)] == h[L - 1 - n])
+                mu = mu + same
+            key = torch.where(mu >= ngram_min, (mu << 32) | e, torch.zeros_like(e))
+            best = int(key.max())
+            if best:
+                end = best & 0xFFFFFFFF
+                nd = max(min(k, L - 1 - end, rem - 1, t_cap - L), 0)
+                if nd:
+                    draft[b, :nd] = hist[b, end + 1:end + 1 + nd]
+        hlen[b], remaining[b], dcnt[b] = L, rem, nd
+        result[b, 0], result[b, 1] = m, nd
+    return result
+
+
+def spec_accept_draft(hist: Tensor, hlen: Tensor, remaining: Tensor, draft: Tensor, dcnt: Tensor,
+                      tok: Optional[Tensor], eos_id: int = -1, k: int = 4, ngram_min: int = 1, ngram_max: int = 3,
+                      t_cap: int = 1 << 30, result: Optional[Tensor] = None) -> Tensor:
+    """One round of speculative decoding for B sequences in one launch (``dta_spec_accept_draft``), on the
+    loop's device state, updated in place: ``hist`` int32 (B, cap) token histories of ``hlen`` tokens each
+    (the last one pending), ``remaining`` tokens still owed (``<= 0``: finished, the row is not touched),
+    ``draft`` int32 (B, k) and its lengths ``dcnt``.  ``tok`` int64 (B, Tn), ``Tn <= k + 1``: the samples of
+    the round's logits rows (row 0 after the pending token, row j after ``draft[j - 1]``), any row stride;
+    None: no rows, only a draft.  The leading drafts that equal their samples are accepted, one more sample
+    is emitted (``eos_id`` or a negative token ends the sequence), the emitted tokens join ``hist``, and the
+    next draft is the continuation of the longest, then latest, earlier occurrence of the history's last
+    ``ngram_min .. ngram_max`` tokens, at most ``min(k, remaining - 1, t_cap - hlen)`` long
+    (``ngram_min = 0``: no lookup, the next ``dcnt`` is 0).  Returns ``result`` int32 (B, 2): (tokens
+    emitted m, next dcnt) -- the cache keeps its old length + m rows.
+
+    CPU tensors, and a library without the entry point, run ``spec_accept_draft_reference``."""
+    if hist.device.type != "cuda" or not spec_supported():
+        return spec_accept_draft_reference(hist, hlen, remaining, draft, dcnt, tok, eos_id, k, ngram_min, ngram_max,
+                                           t_cap, result)
+    if result is None:
+        result = torch.empty(hist.shape[0], 2, dtype=torch.int32, device=hist.device)
+    B, cap, Tn = _spec_check(hist, hlen, remaining, draft, dcnt, tok, result, k, ngram_min, ngram_max, t_cap)
+    if cap > 1 << 30:
+        raise ValueError(f"cap {cap} is above 2^30")
+    if Tn and ((tok.stride(1) != 1 and Tn > 1) or (tok.stride(0) < Tn and B > 1)):
+        tok = tok.contiguous()
+    if B > 0:
+        row = lambda t, n: t.stride(0) if B > 1 else n                                # noqa: E731
+        a = _lib.SpecAcceptDraftArgs(B, Tn, int(k), cap, min(int(t_cap), 1 << 30), int(ngram_min), int(ngram_max),
+                                     max(min(int(eos_id), 2 ** 31 - 1), -1), row(hist, cap), row(draft, int(k)),
+                                     row(tok, Tn) if Tn else 0, hist.data_ptr(), hlen.data_ptr(), remaining.data_ptr(),
+                                     draft.data_ptr(), dcnt.data_ptr(), tok.data_ptr() if Tn else None,
+                                     result.data_ptr())
+        _lib.check(_lib.load().dta_spec_accept_draft(a, _lib.stream_handle(hist.device)))
+    return result
+
+
 # ------------------------------------------------------ shared-prefix decode ---
 # The one-row paged decode for a batch in which groups of sequences have the same pool pages under
 # their first rows (``PagedKVCache.fork``, ``generate_paged(n_samples=k)``): a group pass reads the

@@ -857,6 +857,64 @@ typedef struct dta_sample_rows_args {
 } dta_sample_rows_args;
 int dta_sample_rows(const dta_sample_rows_args* a, void* stream);
 
+/* Speculative decoding: one round's acceptance and the next prompt-lookup draft in one launch (still
+ * ABI 9; the presence of the symbol is the capability check).  One 256-thread workgroup per sequence.
+ * The draft is deterministic, so exact speculative sampling is: draw t from the target distribution
+ * with the uniform the plain loop would use at that position (dta_sample_rows with stream b and
+ * offset = tokens emitted so far + j), accept draft token d iff t == d, otherwise emit t.  The tokens
+ * emitted are therefore the plain loop's, whatever was drafted.
+ * State of sequence b (device int32, owned by the caller's loop, updated in place):
+ *   hist[b][0 .. cap)    token history; hlen_dev[b] tokens of it are set, the last one is pending:
+ *                        emitted, not yet through the model
+ *   remaining_dev[b]     new tokens still owed; <= 0: finished
+ *   draft[b][0 .. K)     the draft the round verified, dcnt_dev[b] tokens of it
+ * Input: tok[b][0 .. Tn), int64, the samples of the round's logits rows: row 0 follows the pending
+ * token, row j follows draft[j - 1].  0 <= Tn <= K + 1 (Tn = 0: no rows to accept, a draft alone).
+ * Clamps, before anything is indexed: hlen into [0, cap], dcnt into [0, min(K, max(Tn - 1, 0))].
+ * Accept.
+ *   1. remaining <= 0: the row is left alone (no byte of its state is written): m = 0, next dcnt = 0.
+ *   2. a = #{leading j < dcnt : tok[b][j] == draft[b][j]},  m = min(a + 1, remaining, Tn, cap - hlen)
+ *      (the last term keeps the append inside hist; a caller that sizes cap >= hlen + remaining
+ *      never meets it).
+ *   3. The emitted tokens are tok[b][0 .. m).
+ *   4. If one of them is eos_id or negative (the sampler's -1 for a degenerate row), m is cut to end
+ *      just after the first such token and remaining becomes 0; otherwise remaining -= m.
+ *   5. hist[b][hlen .. hlen + m) = the emitted tokens (as int32), hlen += m.
+ *   6. The KV cache keeps m of the round's rows, the pending token's and the m - 1 accepted drafts':
+ *      the caller truncates it to its old length + m.
+ * Draft (L = the new hlen, remaining the new one).
+ *   1. ngram_min == 0 (lookup off: the caller drafts), remaining <= 1 or L <= ngram_min: dcnt = 0.
+ *   2. For each end e in [ngram_min - 1, L - 1): mu(e) = the largest n <= min(ngram_max, e + 1) with
+ *      hist[e - t] == hist[L - 1 - t] for all t < n.
+ *   3. Among the ends with mu(e) >= ngram_min the one maximising (mu(e), e) wins -- the longest
+ *      match, then the latest -- found as one 64-bit integer maximum of (mu << 32 | e).
+ *   4. dcnt = max(0, min(K, L - 1 - e, remaining - 1, t_cap - L)), draft[b][0 .. dcnt) =
+ *      hist[e + 1 ..); no such end: dcnt = 0.  Draft entries at and beyond dcnt are not written.
+ * result_out[b] = (m, dcnt), int32 [B][2]: what the host reads back once a round.
+ * A row's outputs are a function of the row alone: independent of B, of the row's index and of
+ * timing (integers only, no atomics).  Nothing outside hist[b][hlen .. hlen + m), draft[b][0 .. dcnt),
+ * the three scalars of an unfinished row and result_out[b] is written.
+ * DTA_ERR_INVALID: B < 0, K outside 1 .. 7, Tn outside 0 .. K + 1, ngram_max outside 1 .. 8,
+ * ngram_min outside 0 .. ngram_max, cap or t_cap outside 1 .. 2^30, a row stride below its row
+ * (hist_stride < cap, draft_stride < K, tok_stride < Tn), a null pointer (tok may be null at Tn = 0)
+ * or one not aligned to its element.  B == 0: DTA_OK, no launch. */
+typedef struct dta_spec_accept_draft_args {
+  int32_t B, Tn, K;
+  int32_t cap;                       /* tokens a row of hist holds */
+  int32_t t_cap;                     /* the model's window (block_size): bounds a draft */
+  int32_t ngram_min, ngram_max;      /* ngram_min 0: no lookup */
+  int32_t eos_id;                    /* or -1 */
+  int64_t hist_stride, draft_stride, tok_stride;   /* elements from one row to the next */
+  int32_t* hist;                     /* device int32 [B][cap] */
+  int32_t* hlen_dev;                 /* device int32 [B] */
+  int32_t* remaining_dev;            /* device int32 [B] */
+  int32_t* draft;                    /* device int32 [B][K] */
+  int32_t* dcnt_dev;                 /* device int32 [B] */
+  const int64_t* tok;                /* device int64 [B][Tn] */
+  int32_t* result_out;               /* device int32 [B][2] */
+} dta_spec_accept_draft_args;
+int dta_spec_accept_draft(const dta_spec_accept_draft_args* a, void* stream);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every
