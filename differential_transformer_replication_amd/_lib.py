@@ -46,7 +46,9 @@ EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_
            # seeded temperature / top-k / top-p sampling of logits rows, added the same way
            "dta_sample_rows",
            # a speculative round's acceptance and next prompt-lookup draft, added the same way
-           "dta_spec_accept_draft")
+           "dta_spec_accept_draft",
+           # the feed and the length commit of a fixed-shape (graph-replayed) speculative round, added the same way
+           "dta_spec_feed_rows", "dta_spec_commit_lengths")
 # the entry points an older library of the same ABI may lack without being unusable
 # (``ops.fp8_cache_supported``)
 FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
@@ -63,6 +65,8 @@ STEP_EXPORTS = ("dta_kv_step_rows",)
 SAMPLE_EXPORTS = ("dta_sample_rows",)
 # and the speculative round's accept + draft kernel (``ops.spec_supported``), added the same way
 SPEC_EXPORTS = ("dta_spec_accept_draft",)
+# and the glue of the fixed-shape round (``ops.spec_round_supported``), added the same way
+SPEC_ROUND_EXPORTS = ("dta_spec_feed_rows", "dta_spec_commit_lengths")
 
 
 class DtaTensor(ctypes.Structure):
@@ -240,6 +244,18 @@ class SpecAcceptDraftArgs(ctypes.Structure):
                                                   "result_out")])
 
 
+class SpecFeedRowsArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("B", "K", "cap", "vocab", "total")]
+                + [(n, ctypes.c_int64) for n in ("hist_stride", "draft_stride", "idx_stride", "offset_stride")]
+                + [(n, ctypes.c_void_p) for n in ("hist", "hlen_dev", "remaining_dev", "draft", "dcnt_dev", "idx_out",
+                                                  "counts_out", "offset_out")])
+
+
+class SpecCommitLengthsArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("B", "K", "t_cap", "n_slots")]
+                + [(n, ctypes.c_void_p) for n in ("lengths", "result", "slots")])
+
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -324,6 +340,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if spec_symbols(lib):
             lib.dta_spec_accept_draft.argtypes = [P(SpecAcceptDraftArgs), ctypes.c_void_p]
             lib.dta_spec_accept_draft.restype = ctypes.c_int
+        if spec_round_symbols(lib):
+            lib.dta_spec_feed_rows.argtypes = [P(SpecFeedRowsArgs), ctypes.c_void_p]
+            lib.dta_spec_feed_rows.restype = ctypes.c_int
+            lib.dta_spec_commit_lengths.argtypes = [P(SpecCommitLengthsArgs), ctypes.c_void_p]
+            lib.dta_spec_commit_lengths.restype = ctypes.c_int
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -368,6 +389,12 @@ def spec_symbols(lib) -> bool:
     """Whether ``lib`` exports the speculative round's accept + draft kernel (it arrived inside ABI 9, after
     the row sampler)."""
     return all(hasattr(lib, name) for name in SPEC_EXPORTS)
+
+
+def spec_round_symbols(lib) -> bool:
+    """Whether ``lib`` exports the feed and the length commit of the fixed-shape speculative round (they
+    arrived inside ABI 9, after the accept + draft kernel)."""
+    return all(hasattr(lib, name) for name in SPEC_ROUND_EXPORTS)
 
 
 def check(rc: int) -> None:

@@ -795,6 +795,40 @@ int dta_spec_accept_draft(const dta_spec_accept_draft_args* a, void* stream) {
   return status(launch_spec(p, (hipStream_t)stream));
 }
 
+int dta_spec_feed_rows(const dta_spec_feed_rows_args* a, void* stream) {
+  if (!a || a->B < 0 || a->K < 1 || a->K > 7 || a->vocab < 1 || a->total < 0) return DTA_ERR_INVALID;
+  if (a->cap < 1 || a->cap > (1 << 30)) return DTA_ERR_INVALID;
+  if (a->hist_stride < a->cap || a->draft_stride < a->K || a->idx_stride < a->K + 1 || a->offset_stride < a->K + 1)
+    return DTA_ERR_INVALID;
+  if (!a->hist || !a->hlen_dev || !a->remaining_dev || !a->draft || !a->dcnt_dev || !a->idx_out || !a->counts_out ||
+      !a->offset_out)
+    return DTA_ERR_INVALID;
+  if ((uintptr_t)a->hist % 4 || (uintptr_t)a->hlen_dev % 4 || (uintptr_t)a->remaining_dev % 4 || (uintptr_t)a->draft % 4 ||
+      (uintptr_t)a->dcnt_dev % 4 || (uintptr_t)a->counts_out % 4 || (uintptr_t)a->idx_out % 8 || (uintptr_t)a->offset_out % 8)
+    return DTA_ERR_INVALID;
+  if (a->B == 0) return DTA_OK;
+  SpecFeedParams p{};
+  p.hist = a->hist; p.hlen = a->hlen_dev; p.remaining = a->remaining_dev; p.draft = a->draft; p.dcnt = a->dcnt_dev;
+  p.idx = a->idx_out; p.counts = a->counts_out; p.offset = a->offset_out;
+  p.hist_stride = a->hist_stride; p.draft_stride = a->draft_stride; p.idx_stride = a->idx_stride;
+  p.offset_stride = a->offset_stride;
+  p.B = a->B; p.K = a->K; p.cap = a->cap; p.vocab = a->vocab; p.total = a->total;
+  return status(launch_spec_feed(p, (hipStream_t)stream));
+}
+
+int dta_spec_commit_lengths(const dta_spec_commit_lengths_args* a, void* stream) {
+  if (!a || a->B < 0 || a->K < 1 || a->K > 7 || a->t_cap < 1 || a->t_cap > (1 << 30) || a->n_slots < 1)
+    return DTA_ERR_INVALID;
+  if (!a->slots && a->n_slots < a->B) return DTA_ERR_INVALID;
+  if (!a->lengths || !a->result) return DTA_ERR_INVALID;
+  if ((uintptr_t)a->lengths % 4 || (uintptr_t)a->result % 4 || (uintptr_t)a->slots % 8) return DTA_ERR_INVALID;
+  if (a->B == 0) return DTA_OK;
+  SpecCommitParams p{};
+  p.lengths = a->lengths; p.result = a->result; p.slots = a->slots;
+  p.B = a->B; p.K = a->K; p.t_cap = a->t_cap; p.n_slots = a->n_slots;
+  return status(launch_spec_commit(p, (hipStream_t)stream));
+}
+
 int dta_extend_supported(int32_t dtype, int32_t head_size, int32_t n_terms, int32_t dv) {
   return extend_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }

@@ -217,6 +217,30 @@ struct SpecParams {
 };
 int launch_spec(const SpecParams& p, hipStream_t st);
 
+// dta_spec_feed_rows (spec_round.hip): a fixed-shape round's tokens, counts and sampler offsets
+struct SpecFeedParams {
+  const int* hist;       // [B][cap], row stride in elements
+  const int* hlen;       // [B], clamped to [0, cap]
+  const int* remaining;  // [B]; <= 0: a finished row
+  const int* draft;      // [B][K]
+  const int* dcnt;       // [B], clamped to [0, K]
+  int64_t* idx;          // [B][K + 1]
+  int* counts;           // [B]
+  int64_t* offset;       // [B][K + 1]
+  int64_t hist_stride, draft_stride, idx_stride, offset_stride;
+  int B, K, cap, vocab, total;
+};
+int launch_spec_feed(const SpecFeedParams& p, hipStream_t st);
+
+// dta_spec_commit_lengths (spec_round.hip): lengths[slot] += the round's emitted tokens
+struct SpecCommitParams {
+  int* lengths;          // [n_slots]
+  const int* result;     // [B][2]
+  const int64_t* slots;  // [B] or null, clamped to [0, n_slots - 1]
+  int B, K, t_cap, n_slots;
+};
+int launch_spec_commit(const SpecCommitParams& p, hipStream_t st);
+
 struct ExtendParams {
   T5 q, k, v, o;       // q/o: Tq rows per (b, h); k/v: the cache [b][t][h][i], rows 0 .. pos+Tq-1 valid
   const float* coef;   // [h][i]

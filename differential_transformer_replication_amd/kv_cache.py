@@ -55,6 +55,9 @@ on (seed, the sequence's stream, its position) only; None keeps the reference's 
 a round that scores the pending token and up to k drafted ones (``append_*(all_rows=True)``), samples every
 row with the offsets the plain loop would use, and lets ``ops.spec_accept_draft`` accept, append and draft
 again on the device (``_speculative_tokens``).  The tokens are the ``sampler`` loop's, token for token.
+``Speculation(graph=True)`` makes every round the same K + 1 rows per sequence and replays it as one captured
+HIP graph (``SpecRound``): ``ops.spec_feed_rows`` builds its inputs and ``ops.spec_commit_lengths`` rolls the
+lengths back on the device, so the host only grows pages before the replay and reads the round's result after.
 """
 from __future__ import annotations
 
@@ -70,7 +73,7 @@ from ._compat import mha_out_scale
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
            "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
-           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler", "Speculation"]
+           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler", "Speculation", "SpecRound"]
 
 
 class Sampler:
@@ -116,10 +119,13 @@ class Speculation:
     (B, cap) histories, their lengths, the tokens still owed; returns an integer (B, k) draft and its (B,)
     lengths, which the loop clips to what the window and ``remaining`` allow).  Immutable; ``stats`` holds
     the counts of the last call: ``rounds`` (model steps), ``drafted`` and ``accepted`` draft tokens,
-    ``emitted`` tokens."""
-    __slots__ = ("k", "ngram_max", "ngram_min", "drafter", "stats")
+    ``emitted`` tokens.  ``graph=True`` (default False: the eager round, as it was): every round runs k + 1
+    rows per sequence and is one replay of a HIP graph captured once per call (``SpecRound``); same tokens,
+    same ``stats``.  It needs ``ops.spec_round_supported()`` on the GPU -- ``RuntimeError`` otherwise, there
+    is no fallback -- and a round whose padded rows would pass ``block_size`` runs eagerly."""
+    __slots__ = ("k", "ngram_max", "ngram_min", "drafter", "stats", "graph")
 
-    def __init__(self, k: int = 4, ngram_max: int = 3, ngram_min: int = 1, drafter=None):
+    def __init__(self, k: int = 4, ngram_max: int = 3, ngram_min: int = 1, drafter=None, graph: bool = False):
         k, ngram_max, ngram_min = int(k), int(ngram_max), int(ngram_min)
         if not 1 <= k <= ops.SPEC_MAX_K:
             raise ValueError(f"k {k} outside 1 .. {ops.SPEC_MAX_K}")
@@ -128,7 +134,7 @@ class Speculation:
         if drafter is not None and not callable(getattr(drafter, "propose", None)):
             raise ValueError("drafter must have propose(hist, hlen, remaining, k) -> (draft, dcnt)")
         for name, v in (("k", k), ("ngram_max", ngram_max), ("ngram_min", ngram_min), ("drafter", drafter),
-                        ("stats", dict(rounds=0, drafted=0, accepted=0, emitted=0))):
+                        ("stats", dict(rounds=0, drafted=0, accepted=0, emitted=0)), ("graph", bool(graph))):
             object.__setattr__(self, name, v)
 
     def __setattr__(self, name, value):
@@ -136,7 +142,7 @@ class Speculation:
 
     def __repr__(self):
         return (f"Speculation(k={self.k}, ngram_max={self.ngram_max}, ngram_min={self.ngram_min}, "
-                f"drafter={self.drafter!r})")
+                f"drafter={self.drafter!r}" + (", graph=True)" if self.graph else ")"))
 
 
 def _stream_ids(streams, B: int, n_samples: int, device) -> Optional[torch.Tensor]:
@@ -424,6 +430,91 @@ def _seq_graph(model, cache, B: int, masked: bool, device, slots: Optional[torch
     if g is None:
         g = cache.graphs[(B, masked)] = SeqDecodeGraph(model, cache, B, device, slots)
     return g
+
+
+class SpecRound:
+    """``SeqDecodeGraph`` for a speculative round (``Speculation(graph=True)``): the round of
+    ``_speculative_tokens`` at a fixed shape, K + 1 rows per sequence, captured once per call of
+    ``generate_ragged`` / ``generate_paged`` and replayed for every round.  It holds by address the loop's
+    state (``hist``, ``hlen``, ``remaining``, ``draft``, ``dcnt``, ``result``), its static buffers (``idx``
+    (B, K + 1) long, ``counts`` (B,) int32, ``offset`` (B, K + 1) long, ``stream`` the (B * (K + 1),) stream
+    ids, ``tok`` the round's samples) and, paged, ``slots`` (B,) long: the rows of ``cache.block_table`` /
+    ``cache.lengths`` of the call's sequences.  The body, in order: ``ops.spec_feed_rows``; paged, the gather
+    of the table rows and lengths; ``_ragged_model_step`` / ``_paged_model_step`` over the (B, K + 1) tokens
+    (reached by their module names at call time; the lengths are not advanced); ``ops.sample_rows`` of all
+    B * (K + 1) rows with the sampler's scalars and the device ``stream`` / ``offset``; ``ops.spec_accept_draft``
+    with ``Tn = K + 1``; ``ops.spec_commit_lengths``, the only writer of the lengths.  No host value shapes
+    it.  Page growth and copy on write stay on the host, before the replay; a ``drafter`` proposes after it.
+
+    A fixed ``Tn = K + 1`` gives the (m, dcnt), history and drafts of the eager round's ``Tn = max(dcnt) + 1``:
+    in the header's accept rule ``a <= dcnt <= Tn - 1`` either way, so ``min(a + 1, remaining, Tn, cap - hlen)``
+    never takes its ``Tn`` term, and the rows past ``dcnt`` -- padding here -- are never looked at.
+
+    On a CUDA device the body is warmed up on a side stream and captured on one stream (no parallel
+    branches).  The warm-up runs for real, so it is made inert: ``remaining`` is saved and zeroed for warm-up
+    and capture, every sequence is then not live (``counts = 0``, ``m = 0``: nothing is cached, accepted or
+    moved), and it is restored after.  The graph holds the cache's pools (or rows), ``block_table``,
+    ``lengths`` and ``cache.consts`` by address, as ``SeqDecodeGraph`` does.  On CPU tensors the same body
+    runs uncaptured, through the ops' references."""
+
+    def __init__(self, model, cache: "KVCache", sampler: Sampler, spec: Speculation, state, total: int, vocab: int,
+                 eos: int, stream: torch.Tensor, slots: Optional[torch.Tensor] = None):
+        self.hist, self.hlen, self.remaining, self.draft, self.dcnt, self.result = state
+        dev = self.hist.device
+        if dev.type == "cuda" and not (ops.spec_round_supported() and ops.spec_supported()):
+            raise RuntimeError("Speculation(graph=True) needs dta_spec_feed_rows, dta_spec_commit_lengths and "
+                               "dta_spec_accept_draft, which this libdiffattn.so does not export "
+                               "(ops.spec_round_supported); there is no fallback")
+        if cache.lengths is None:
+            raise ValueError("a speculative round needs a prefilled cache")
+        self.model, self.cache, self.sampler, self.spec = model, cache, sampler, spec
+        self.total, self.vocab, self.eos, self.bs = int(total), int(vocab), int(eos), model.block_size
+        B, K = self.hist.shape[0], spec.k
+        self.paged = slots is not None
+        self.slots = slots.clone() if self.paged else None
+        self.idx = torch.zeros(B, K + 1, dtype=torch.long, device=dev)
+        self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.offset = torch.zeros(B, K + 1, dtype=torch.long, device=dev)
+        self.stream = stream[:, None].expand(B, K + 1).reshape(-1).contiguous()
+        self.tok = None
+        self.graph = None
+        if dev.type != "cuda":
+            return
+        owed = self.remaining.clone()
+        self.remaining.zero_()                     # inert: no sequence is live
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._body()
+        self.remaining.copy_(owed)
+
+    def _body(self) -> None:
+        cache, spec, smp, K = self.cache, self.spec, self.sampler, self.spec.k
+        B = self.hist.shape[0]
+        ops.spec_feed_rows(self.hist, self.hlen, self.remaining, self.draft, self.dcnt, K, self.vocab, self.total,
+                           self.idx, self.counts, self.offset)
+        if self.paged:
+            tbl = cache.block_table.index_select(0, self.slots)
+            pos = cache.lengths.index_select(0, self.slots)
+            rows = _paged_model_step(self.model, self.idx, cache, tbl, pos, self.counts)
+        else:
+            rows = _ragged_model_step(self.model, self.idx, cache, cache.lengths, self.counts)
+        self.tok = ops.sample_rows(rows, smp.temperature, smp.top_k, smp.top_p, smp.seed, self.stream,
+                                   self.offset.reshape(-1)).reshape(B, K + 1)
+        ops.spec_accept_draft(self.hist, self.hlen, self.remaining, self.draft, self.dcnt, self.tok, self.eos, K,
+                              spec.ngram_min if spec.drafter is None else 0, spec.ngram_max, self.bs, self.result)
+        ops.spec_commit_lengths(cache.lengths, self.result, K, self.bs, self.slots)
+
+    def run(self) -> None:
+        """One round on the state as it stands: a replay, or on CPU tensors the body itself."""
+        if self.graph is None:
+            self._body()
+        else:
+            self.graph.replay()
 
 
 def _model_step(model, idx: torch.Tensor, cache: KVCache, pos: int, all_rows: bool = False) -> torch.Tensor:
@@ -855,7 +946,8 @@ def _check_speculate(speculate, sampler, n_samples: int = 1, shared_decode: bool
 
 
 def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[int], sampler: Sampler,
-                        streams: Optional[torch.Tensor], spec: Speculation, bs: int, append, truncate):
+                        streams: Optional[torch.Tensor], spec: Speculation, bs: int, append, truncate,
+                        fixed=None):
     """``_sample_tokens`` by speculative rounds, for ``max_new_tokens >= 1``.  ``logits`` (B, vocab) are the
     prefill's; ``append(new_idx, counts)`` is the cache's multi-row step with ``all_rows=True`` and
     ``truncate(lengths)`` its roll-back.  Per sequence the device holds the token history (prompt and
@@ -865,7 +957,15 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
     tokens emitted so far + j), the plain loop's -- runs one ``ops.spec_accept_draft`` and reads one
     small tensor back ((m, next dcnt) and the tokens still owed), then truncates each cache to its old
     length + m.  The first token comes from the prefill's logits through the same kernel, with no draft
-    to accept.  Returns the histories: a list of B int64 tensors, prompt included."""
+    to accept.  Returns the histories: a list of B int64 tensors, prompt included.
+
+    ``fixed``: with ``spec.graph``, the (model, cache, the paged call's sequence ids or None) a ``SpecRound``
+    is made from.  A round then does the host's work first -- paged: ``_check_live``, the pages of its
+    ``dcnt + 1`` rows (exact: ``dcnt`` came back with the last read), ``_flush`` -- then replays, reads the
+    same small tensor back and settles the host's copy of the lengths (``PagedKVCache._rolled_back``; the
+    device lengths are already right).  A round in which a live sequence has ``length + K + 1 > block_size``
+    -- its padded rows would not fit the window -- takes the eager path above on the same state; the two
+    give the same tokens, so they may interleave."""
     dev = logits.device
     B, K = len(prompts), spec.k
     lens = [int(p.shape[0]) for p in prompts]
@@ -887,6 +987,9 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
     def accept(tok):
         ops.spec_accept_draft(hist, hlen, remaining, draft, dcnt, tok, eos, K, spec.ngram_min if lookup else 0,
                               spec.ngram_max, bs, result)
+        return read_back()
+
+    def read_back():
         if not lookup:
             d, n = spec.drafter.propose(hist, hlen, remaining, K)
             room = torch.minimum(remaining - 1, bs - hlen).clamp(0, K)
@@ -901,8 +1004,34 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
     m, dc, rem = accept(tok)
     stats["emitted"] += sum(m)
     cols = torch.arange(K, device=dev)
+    fixed_round = None
+    if spec.graph and any(r > 0 for r in rem):
+        model, cache, seqs = fixed
+        slots = None if seqs is None else torch.tensor([cache.slot[q] for q in seqs], device=dev)
+        fixed_round = SpecRound(model, cache, sampler, spec, (hist, hlen, remaining, draft, dcnt, result),
+                                max_new_tokens, logits.shape[-1], eos, strm, slots)
     while any(r > 0 for r in rem):
         counts = [d + 1 if r > 0 else 0 for d, r in zip(dc, rem)]
+        if fixed_round is not None and all(n + K + 1 <= bs for n, r in zip(have, rem) if r > 0):
+            if seqs is not None:                                 # page growth and copy on write: the host's, first
+                cache._check_live(seqs)
+                writers = [b for b in range(B) if counts[b] > 0]
+                cache._prepare_writes([seqs[b] for b in writers], [have[b] + counts[b] for b in writers])
+                cache._flush()
+            fixed_round.run()
+            m, dc_next, rem = read_back()
+            have = [n + k for n, k in zip(have, m)]
+            if seqs is None:
+                cache.host_lengths = list(have)
+            else:
+                for q, n in zip(seqs, have):
+                    cache._rolled_back(q, n)
+            stats["rounds"] += 1
+            stats["drafted"] += sum(c - 1 for c in counts if c)
+            stats["accepted"] += sum(k - 1 for k in m if k)
+            stats["emitted"] += sum(m)
+            dc = dc_next
+            continue
         Tn = max(counts)
         pending = hist.gather(1, (hlen.long() - 1).clamp_(min=0)[:, None])
         drafted = torch.where(cols[None, :Tn - 1] < dcnt[:, None], draft[:, :Tn - 1], 0)
@@ -1039,7 +1168,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     drafts are accepted.  The cache is then made with ``rows_decode=True``, so a round of 2 .. 8 rows that
     has a plan reads the cache once and every row is the one-row decode's; ``graph`` / ``fused_step`` keep
     their meaning for one-token steps and rounds do not use the graph; a round reads three small integers
-    per sequence back."""
+    per sequence back.  ``Speculation(graph=True)`` replays each round as one captured HIP graph of K + 1 rows
+    per sequence (``SpecRound``); the cache then keeps the storage of ``lengths`` as with ``graph=True``."""
     bs = model.block_size
     if speculate is not None:
         _check_speculate(speculate, sampler)
@@ -1047,7 +1177,8 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
                              f"block_size {bs}: the sliding window is the one-length path's job")
-    cache = RaggedKVCache(rows_decode=speculate is not None, graph=graph, fused_step=fused_step)
+    cache = RaggedKVCache(rows_decode=speculate is not None,
+                          graph=graph or (speculate is not None and speculate.graph), fused_step=fused_step)
     logits = prefill_ragged(model, prompts, cache)
     if max_new_tokens < 1:
         return [p.clone() for p in prompts]
@@ -1055,7 +1186,7 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
                                    _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
                                    lambda idx, counts: append_ragged(model, idx, counts, cache, all_rows=True),
-                                   cache.truncate)
+                                   cache.truncate, (model, cache, None))
         return [o.to(p.device) for o, p in zip(outs, prompts)]
     toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
                                 lambda tok, active: decode_ragged(model, tok, cache, active), sampler,
@@ -1433,6 +1564,14 @@ class PagedKVCache(KVCache):
         self._trim(seq)
         self._shared_key = None                    # a kept plan's rows were cut to the lengths before
 
+    def _rolled_back(self, seq: int, new_length: int) -> None:
+        """The host half of ``truncate`` after a round whose lengths the device has already settled
+        (``SpecRound``: ``ops.spec_commit_lengths``): ``seq`` holds ``new_length`` rows, the whole pages past
+        them are returned.  No length is marked for upload."""
+        self.host_lengths[seq] = self.host_low[seq] = int(new_length)
+        self._trim(seq)
+        self._shared_key = None                    # a kept plan's rows were cut to the lengths before
+
     def fork(self, seq: int) -> int:
         """A new sequence with the same content as ``seq``, sharing every one of its
         pages, a partial last page included (each refcount goes up by one; no device
@@ -1594,7 +1733,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     ``b * n_samples + j`` (``streams[b] * n_samples + j``), so the forks of one prompt differ.
     ``speculate``: ``generate_ragged``'s (not with ``n_samples > 1`` or ``shared_decode``); the pool is made
     with ``rows_decode=True``, a round takes pages for its drafted rows and ``truncate`` returns those of
-    the rejected ones, so the default ``num_pages`` still holds the call."""
+    the rejected ones, so the default ``num_pages`` still holds the call; with ``Speculation(graph=True)`` the
+    pages are taken before the round's replay and returned after the read of its result."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
@@ -1624,7 +1764,7 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
         outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
                                    _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
                                    lambda idx, counts: append_paged(model, roots, idx, counts, cache, all_rows=True),
-                                   roll_back)
+                                   roll_back, (model, cache, roots))
         return [o.to(p.device) for o, p in zip(outs, prompts)]
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]

@@ -1658,6 +1658,162 @@ def spec_accept_draft(hist: Tensor, hlen: Tensor, remaining: Tensor, draft: Tens
     return result
 
 
+# The glue of a fixed-shape round (always k + 1 rows per sequence), so that no host value shapes it and it can
+# be captured once and replayed (``kv_cache.SpecRound``): the round's tokens, counts and sampler offsets from
+# the state above, and the cache lengths after the accept.  include/diffattn.h ("A fixed-shape speculative
+# round") is the definition; the ``*_reference`` functions are the same definition in torch.
+def spec_round_supported() -> bool:
+    """Whether the loaded library has ``dta_spec_feed_rows`` and ``dta_spec_commit_lengths`` (an older build
+    of the same ABI may not)."""
+    return _lib.spec_round_symbols(_lib.load())
+
+
+def _need_spec_round(device) -> None:
+    if not spec_round_supported():
+        raise RuntimeError("this libdiffattn.so exports no dta_spec_feed_rows / dta_spec_commit_lengths "
+                           f"(ops.spec_round_supported); there is no fallback on {device}")
+
+
+def _spec_feed_check(hist, hlen, remaining, draft, dcnt, k, vocab, total, idx_out, counts_out, offset_out):
+    """The shapes and values both implementations insist on; returns (B, cap, idx_out, counts_out, offset_out),
+    the outputs allocated where they were not given."""
+    k, vocab, total = int(k), int(vocab), int(total)
+    if not 1 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k {k} outside 1 .. {SPEC_MAX_K}")
+    if vocab < 1 or total < 0 or vocab > 2 ** 31 - 1 or total > 2 ** 31 - 1:
+        raise ValueError(f"need 1 <= vocab {vocab} and 0 <= total {total}, both int32")
+    if hist.dim() != 2 or hist.shape[1] < 1:
+        raise ValueError("hist must be (B, cap) with cap >= 1")
+    B, cap = hist.shape
+    dev = hist.device
+    if idx_out is None:
+        idx_out = torch.empty(B, k + 1, dtype=torch.int64, device=dev)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=dev)
+    if offset_out is None:
+        offset_out = torch.empty(B, k + 1, dtype=torch.int64, device=dev)
+    for name, t, shape, dt in (("hist", hist, (B, cap), torch.int32), ("hlen", hlen, (B,), torch.int32),
+                               ("remaining", remaining, (B,), torch.int32), ("draft", draft, (B, k), torch.int32),
+                               ("dcnt", dcnt, (B,), torch.int32), ("idx_out", idx_out, (B, k + 1), torch.int64),
+                               ("counts_out", counts_out, (B,), torch.int32),
+                               ("offset_out", offset_out, (B, k + 1), torch.int64)):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{name} must be a {dt} {shape} tensor on {dev}")
+        if (t.stride(-1) != 1 and t.shape[-1] > 1) or (t.dim() == 2 and B > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{name} must have contiguous rows that do not overlap")
+    for name, t in (("hlen", hlen), ("remaining", remaining), ("dcnt", dcnt), ("counts_out", counts_out)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return B, cap, idx_out, counts_out, offset_out
+
+
+def spec_feed_rows_reference(hist: Tensor, hlen: Tensor, remaining: Tensor, draft: Tensor, dcnt: Tensor, k: int,
+                             vocab: int, total: int, idx_out: Optional[Tensor] = None,
+                             counts_out: Optional[Tensor] = None, offset_out: Optional[Tensor] = None):
+    """``spec_feed_rows`` in torch, on the tensors' device: include/diffattn.h's definition over the whole
+    batch.  The tests' oracle, and what ``spec_feed_rows`` runs on CPU tensors."""
+    B, cap, idx_out, counts_out, offset_out = _spec_feed_check(hist, hlen, remaining, draft, dcnt, k, vocab, total,
+                                                               idx_out, counts_out, offset_out)
+    k, vocab, total = int(k), int(vocab), int(total)
+    L = hlen.clamp(0, cap)
+    live = (remaining > 0) & (L >= 1)
+    zero = torch.zeros_like(L)
+    d = torch.where(live, dcnt.clamp(0, k), zero)
+    counts_out.copy_(torch.where(live, d + 1, zero))
+    pending = hist.gather(1, (L.long() - 1).clamp_(min=0)[:, None])[:, 0].clamp(0, vocab - 1)
+    idx_out[:, 0] = torch.where(live, pending, zero).long()
+    j = torch.arange(1, k + 1, device=hist.device)
+    idx_out[:, 1:] = torch.where(j[None, :] <= d[:, None], draft.clamp(0, vocab - 1), 0).long()
+    offset_out.copy_((total - remaining.long())[:, None] + torch.arange(k + 1, device=hist.device)[None, :])
+    return idx_out, counts_out, offset_out
+
+
+def spec_feed_rows(hist: Tensor, hlen: Tensor, remaining: Tensor, draft: Tensor, dcnt: Tensor, k: int, vocab: int,
+                   total: int, idx_out: Optional[Tensor] = None, counts_out: Optional[Tensor] = None,
+                   offset_out: Optional[Tensor] = None):
+    """The model inputs of one fixed-shape round of B sequences in one launch (``dta_spec_feed_rows``), from
+    the state ``spec_accept_draft`` keeps, none of it read on the host: ``idx_out`` int64 (B, k + 1), the
+    pending token ``hist[b, hlen[b] - 1]`` followed by the ``dcnt[b]`` drafted ones and zeros, each clamped
+    into ``[0, vocab - 1]``; ``counts_out`` int32 (B,), ``dcnt[b] + 1`` real rows, 0 for a sequence with
+    ``remaining[b] <= 0`` (or no history); ``offset_out`` int64 (B, k + 1), ``total - remaining[b] + j``:
+    the ``sample_rows`` offset of the plain loop at row j.  Every entry of the three is written.  The
+    outputs may be given (any row stride; what a captured graph holds by address).  Returns
+    (idx_out, counts_out, offset_out).
+
+    CPU tensors run ``spec_feed_rows_reference``; on the GPU a library without the entry point is a
+    ``RuntimeError``."""
+    if hist.device.type != "cuda":
+        return spec_feed_rows_reference(hist, hlen, remaining, draft, dcnt, k, vocab, total, idx_out, counts_out,
+                                        offset_out)
+    _need_spec_round(hist.device)
+    B, cap, idx_out, counts_out, offset_out = _spec_feed_check(hist, hlen, remaining, draft, dcnt, k, vocab, total,
+                                                               idx_out, counts_out, offset_out)
+    if cap > 1 << 30:
+        raise ValueError(f"cap {cap} is above 2^30")
+    if B > 0:
+        row = lambda t, n: t.stride(0) if B > 1 else n                                # noqa: E731
+        a = _lib.SpecFeedRowsArgs(B, int(k), cap, int(vocab), int(total), row(hist, cap), row(draft, int(k)),
+                                  row(idx_out, int(k) + 1), row(offset_out, int(k) + 1), hist.data_ptr(),
+                                  hlen.data_ptr(), remaining.data_ptr(), draft.data_ptr(), dcnt.data_ptr(),
+                                  idx_out.data_ptr(), counts_out.data_ptr(), offset_out.data_ptr())
+        _lib.check(_lib.load().dta_spec_feed_rows(a, _lib.stream_handle(hist.device)))
+    return idx_out, counts_out, offset_out
+
+
+def _spec_commit_check(lengths, result, k, t_cap, slots):
+    k, t_cap = int(k), int(t_cap)
+    if not 1 <= k <= SPEC_MAX_K:
+        raise ValueError(f"k {k} outside 1 .. {SPEC_MAX_K}")
+    if t_cap < 1:
+        raise ValueError("t_cap must be >= 1")
+    if lengths.dim() != 1 or lengths.shape[0] < 1 or lengths.dtype != torch.int32 or not lengths.is_contiguous():
+        raise ValueError("lengths must be a contiguous int32 (n_slots,) tensor, n_slots >= 1")
+    dev = lengths.device
+    if result.dim() != 2 or result.shape[1] != 2 or result.dtype != torch.int32 or result.device != dev \
+            or not result.is_contiguous():
+        raise ValueError(f"result must be a contiguous int32 (B, 2) tensor on {dev}")
+    B = result.shape[0]
+    if slots is None:
+        if B > lengths.shape[0]:
+            raise ValueError(f"{B} sequences for {lengths.shape[0]} lengths")
+    elif tuple(slots.shape) != (B,) or slots.dtype != torch.int64 or slots.device != dev or not slots.is_contiguous():
+        raise ValueError(f"slots must be a contiguous int64 ({B},) tensor on {dev}")
+    return B
+
+
+def spec_commit_lengths_reference(lengths: Tensor, result: Tensor, k: int, t_cap: int,
+                                  slots: Optional[Tensor] = None) -> Tensor:
+    """``spec_commit_lengths`` in torch, on the tensors' device, in place.  The tests' oracle, and what
+    ``spec_commit_lengths`` runs on CPU tensors."""
+    B = _spec_commit_check(lengths, result, k, t_cap, slots)
+    if B == 0:
+        return lengths
+    s = torch.arange(B, device=lengths.device) if slots is None else slots.clamp(0, lengths.shape[0] - 1)
+    new = (lengths[s].long() + result[:, 0].clamp(0, int(k) + 1).long()).clamp_(max=int(t_cap))
+    lengths[s] = new.to(torch.int32)
+    return lengths
+
+
+def spec_commit_lengths(lengths: Tensor, result: Tensor, k: int, t_cap: int, slots: Optional[Tensor] = None) -> Tensor:
+    """The device half of a round's roll-back, in one launch (``dta_spec_commit_lengths``): the round's model
+    step leaves the cache's ``lengths`` int32 (n_slots,) alone, and this adds what the round emitted,
+    ``lengths[s] = min(lengths[s] + clamp(result[b, 0], 0, k + 1), t_cap)`` with ``s = slots[b]`` (int64 (B,),
+    distinct, clamped into the tensor; None: ``s = b``) and ``result`` the (B, 2) output of
+    ``spec_accept_draft``.  An entry no sequence names is not touched.  In place; returns ``lengths``.
+
+    CPU tensors run ``spec_commit_lengths_reference``; on the GPU a library without the entry point is a
+    ``RuntimeError``."""
+    if lengths.device.type != "cuda":
+        return spec_commit_lengths_reference(lengths, result, k, t_cap, slots)
+    _need_spec_round(lengths.device)
+    B = _spec_commit_check(lengths, result, k, t_cap, slots)
+    if B > 0:
+        a = _lib.SpecCommitLengthsArgs(B, int(k), min(int(t_cap), 1 << 30), lengths.shape[0], lengths.data_ptr(),
+                                       result.data_ptr(), _lib.ptr(slots))
+        _lib.check(_lib.load().dta_spec_commit_lengths(a, _lib.stream_handle(lengths.device)))
+    return lengths
+
+
 # ------------------------------------------------------ shared-prefix decode ---
 # The one-row paged decode for a batch in which groups of sequences have the same pool pages under
 # their first rows (``PagedKVCache.fork``, ``generate_paged(n_samples=k)``): a group pass reads the

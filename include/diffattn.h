@@ -915,6 +915,65 @@ typedef struct dta_spec_accept_draft_args {
 } dta_spec_accept_draft_args;
 int dta_spec_accept_draft(const dta_spec_accept_draft_args* a, void* stream);
 
+/* A fixed-shape speculative round: the two pieces of glue that let one round -- always K + 1 rows per
+ * sequence -- be captured as a graph and replayed, no host value shaping it (still ABI 9; the presence
+ * of each symbol is the capability check).  Integers only, 64-bit address arithmetic, no atomics; every
+ * device value is clamped before it forms an address.
+ *
+ * dta_spec_feed_rows builds the round's model inputs from the state dta_spec_accept_draft keeps.
+ * Per sequence b, with T = K + 1:
+ *   L      = clamp(hlen_dev[b], 0, cap)
+ *   live   = remaining_dev[b] > 0 && L >= 1
+ *   d      = live ? clamp(dcnt_dev[b], 0, K) : 0
+ *   counts_out[b]    (int32) = live ? d + 1 : 0
+ *   idx_out[b][0]    (int64) = live ? clamp(hist[b][L - 1], 0, vocab - 1) : 0      the pending token
+ *   idx_out[b][j]    (int64) = j <= d ? clamp(draft[b][j - 1], 0, vocab - 1) : 0   for 1 <= j <= K
+ *   offset_out[b][j] (int64) = (int64)total - (int64)remaining_dev[b] + j          for 0 <= j < T
+ * total is the call's number of new tokens, so offset_out[b][j] is the dta_sample_rows offset of the
+ * plain loop at that position (tokens emitted so far + j); the difference is taken in 64 bits, so no
+ * device value overflows it.  All T entries of idx_out[b] and offset_out[b] are written, padding
+ * included: a replay never reads a stale value.  hist[b][L - 1] is loaded only for a live row and
+ * draft[b][j - 1] only for j <= d.  Nothing else is written; a row's outputs are a function of the row
+ * alone.
+ * DTA_ERR_INVALID: B < 0, K outside 1 .. 7, vocab < 1, total < 0, cap outside 1 .. 2^30, a row stride
+ * below its row (hist_stride < cap, draft_stride < K, idx_stride < K + 1, offset_stride < K + 1), a
+ * null pointer or one not aligned to its element.  B == 0: DTA_OK, no launch. */
+typedef struct dta_spec_feed_rows_args {
+  int32_t B, K;
+  int32_t cap;                       /* tokens a row of hist holds */
+  int32_t vocab;                     /* tokens are clamped into [0, vocab - 1] */
+  int32_t total;                     /* the call's max_new_tokens */
+  int64_t hist_stride, draft_stride, idx_stride, offset_stride;   /* elements from one row to the next */
+  const int32_t* hist;               /* device int32 [B][cap] */
+  const int32_t* hlen_dev;           /* device int32 [B] */
+  const int32_t* remaining_dev;      /* device int32 [B] */
+  const int32_t* draft;              /* device int32 [B][K] */
+  const int32_t* dcnt_dev;           /* device int32 [B] */
+  int64_t* idx_out;                  /* device int64 [B][K + 1] */
+  int32_t* counts_out;               /* device int32 [B] */
+  int64_t* offset_out;               /* device int64 [B][K + 1] */
+} dta_spec_feed_rows_args;
+int dta_spec_feed_rows(const dta_spec_feed_rows_args* a, void* stream);
+
+/* dta_spec_commit_lengths is the device half of the cache's roll-back: the round's model step leaves
+ * the cache lengths where they were, and this launch, their only writer in a round, advances each by
+ * what dta_spec_accept_draft emitted.  For each b:
+ *   s = slots ? clamp(slots[b], 0, n_slots - 1) : b
+ *   lengths[s] = min(lengths[s] + clamp(result[b][0], 0, K + 1), t_cap)      (the sum in 64 bits)
+ * result is dta_spec_accept_draft's result_out, int32 [B][2], packed.  The caller guarantees that the
+ * slots are distinct; an entry of lengths that no b names is not touched.
+ * DTA_ERR_INVALID: B < 0, K outside 1 .. 7, t_cap outside 1 .. 2^30, n_slots < 1, n_slots < B without
+ * slots, a null lengths or result, a pointer not aligned to its element.  B == 0: DTA_OK, no launch. */
+typedef struct dta_spec_commit_lengths_args {
+  int32_t B, K;
+  int32_t t_cap;                     /* the model's window: no length passes it */
+  int32_t n_slots;                   /* entries of lengths */
+  int32_t* lengths;                  /* device int32 [n_slots] */
+  const int32_t* result;             /* device int32 [B][2]: (m, next dcnt) */
+  const int64_t* slots;              /* device int64 [B], or null: sequence b is entry b */
+} dta_spec_commit_lengths_args;
+int dta_spec_commit_lengths(const dta_spec_commit_lengths_args* a, void* stream);
+
 /* SwiGLU of the Block feed-forward (diff_transformer.py SwiGLU.forward,
  * Ndiff_transformer.py:86-93 equivalent, control.py:80-90): out = silu(a) * b over
  * rows x n elements (n % 8 == 0; every row stride a multiple of 8 elements, every

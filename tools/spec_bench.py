@@ -19,8 +19,16 @@ rates below are forced.  B in 1, 8, 64; every sequence at length 512 or 4096; pa
                the whole call and with the time of a one-token call (the prefill) taken off; the rate
                reached (accepted / drafted) is reported next to the one asked for, since a bf16 round's
                logits need not pick the recorded token.
+  (d) round_graph  section (a) again with the graph-replayed round (``Speculation(graph=True)``'s ``SpecRound`` on
+               a ``rows_decode``, ``fused_step`` pool: pages and flush on the host, one replay, the read of the
+               result, the host half of the roll-back) at K = 3 and K = 7 next to the eager round, the eager
+               step twice and the ``graph=True, fused_step=True`` step, all taking turns inside every window.
+               ``capture_ms_k*``: the warm-up and the capture, once per call, not part of a round's time.
+               Not part of the default cases; its rows go to ``--graph-out``.
 Usage: python tools/spec_bench.py [--out profiles/spec_bench.json] [--repeats 6] [--warmup 2] [--inner 5]
-       [--batches 1,8,64] [--lengths 512,4096] [--new 48]
+       [--batches 1,8,64] [--lengths 512,4096] [--new 48] [--cases accept,round,generate]
+       python tools/spec_bench.py --cases round_graph --repeats 7 --inner 20
+       [--graph-out profiles/spec_round_graph_bench.json]
 -> one JSON line per case (also written to FILE as a JSON list)."""
 import argparse
 import json
@@ -103,6 +111,84 @@ def round_case(model, B, length, repeats, warmup, inner):
         r = row[f"round_k{k}_ms"]
         row[f"break_even_tokens_k{k}_vs_eager"] = round(r / row["eager_ms"], 3)
         row[f"break_even_tokens_k{k}_vs_graph_fused"] = round(r / row["graph_fused_ms"], 3)
+    return row
+
+
+def _graph_round_fn(model, cache, ids, K, g):
+    """``_round_fn``'s round as ``Speculation(graph=True)`` runs it: the host takes the pages of the K + 1 rows
+    and flushes, one ``SpecRound`` replay, the read of the result, the host half of the roll-back.  The draft is
+    reset to random tokens before every round (one more small launch than the eager arm makes), so that the
+    round's own lookup does not feed an untrained model its own repetitions and the cache grows by about one
+    row a round, as the other arms' do.  Returns (fn, ms the warm-up and the capture took)."""
+    B = len(ids)
+    hist = torch.randint(0, VOCAB, (B, BLOCK), generator=g).to(DEV, torch.int32)
+    hlen = torch.tensor([cache.host_lengths[q] + 1 for q in ids], dtype=torch.int32, device=DEV)
+    draft0 = torch.randint(0, VOCAB, (B, K), generator=g).to(DEV, torch.int32)
+    draft = draft0.clone()
+    back = torch.zeros(3 * B, dtype=torch.int32, device=DEV)
+    result, remaining = back[:2 * B].view(B, 2), back[2 * B:]
+    dcnt = torch.full((B,), K, dtype=torch.int32, device=DEV)
+    slots = torch.tensor([cache.slot[q] for q in ids], device=DEV)
+    cache._flush()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rnd = kv_cache.SpecRound(model, cache, SMP, kv_cache.Speculation(k=K, graph=True),
+                             (hist, hlen, remaining, draft, dcnt, result), 1 << 20, VOCAB, -1,
+                             torch.arange(B, dtype=torch.int64, device=DEV), slots)
+    torch.cuda.synchronize()
+    capture_ms = (time.perf_counter() - t0) * 1e3
+
+    def fn():
+        have = [cache.host_lengths[q] for q in ids]
+        remaining.fill_(1 << 20)
+        dcnt.fill_(K)
+        draft.copy_(draft0)
+        hlen.fill_(min(have) + 1)
+        cache._prepare_writes(ids, [n + K + 1 for n in have])
+        cache._flush()
+        rnd.run()
+        m = back.tolist()[0:2 * B:2]
+        for q, n, k in zip(ids, have, m):
+            cache._rolled_back(q, n + k)
+    return fn, capture_ms
+
+
+@torch.no_grad()
+def round_graph_case(model, B, length, repeats, warmup, inner):
+    """Section (a)'s arms and the graph-replayed round next to them, taking turns inside every window."""
+    g = torch.Generator().manual_seed(B + length)
+    prompts = [torch.randint(0, VOCAB, (length,), generator=g).to(DEV) for _ in range(B)]
+    tok = torch.randint(0, VOCAB, (B, 1), generator=g).to(DEV)
+    steps = 16 + 1 + (warmup + repeats) * inner
+    if length + steps + 8 > BLOCK:
+        raise SystemExit(f"(warmup + repeats) * inner = {(warmup + repeats) * inner} rows do not fit the window")
+    fast = {"rows_decode": True, "fused_step": True}
+    arms = {"eager": {}, "round_k3": {"rows_decode": True}, "graph_round_k3": fast,
+            "round_k7": {"rows_decode": True}, "graph_round_k7": fast,
+            "graph_fused": {"graph": True, "fused_step": True}, "eager_again": {}}
+    caches = {arm: _cache(model, prompts, steps, **flags) for arm, flags in arms.items()}
+    fns, capture = {}, {}
+    for arm, (c, ids) in caches.items():
+        if arm.startswith("graph_round"):
+            fns[arm], capture[arm] = _graph_round_fn(model, c, ids, int(arm[-1]), g)
+        elif arm.startswith("round"):
+            fns[arm] = _round_fn(model, c, ids, int(arm[-1]), g)
+        else:
+            fns[arm] = lambda c=c, ids=ids: kv_cache.decode_paged(model, ids, tok, c)
+    for fn in fns.values():
+        fn()                                       # captures the one-token graph
+    row = {"case": "round_graph", "model": "DiffTransformer cfg1", "dtype": "bf16", "B": B, "length": length,
+           "page_size": P, "repeats": repeats, "warmup": warmup, "inner": inner}
+    _report(row, interleaved_ms(fns, repeats, warmup, inner))
+    row["band_ms"] = round(abs(row["eager_ms"] - row["eager_again_ms"]), 5)
+    row["rows_grown"] = {arm: max(c.host_lengths.values()) - length for arm, (c, _) in caches.items()}
+    for k in (3, 7):
+        r, gr = row[f"round_k{k}_ms"], row[f"graph_round_k{k}_ms"]
+        row[f"capture_ms_k{k}"] = round(capture[f"graph_round_k{k}"], 2)
+        row[f"graph_round_k{k}_below_eager_round_ms"] = round(r - gr, 5)
+        row[f"graph_round_k{k}_wins_by_more_than_band"] = bool(r - gr > row["band_ms"])
+        row[f"break_even_tokens_k{k}_eager_round_vs_graph_fused"] = round(r / row["graph_fused_ms"], 3)
+        row[f"break_even_tokens_k{k}_graph_round_vs_graph_fused"] = round(gr / row["graph_fused_ms"], 3)
     return row
 
 
@@ -247,6 +333,8 @@ def main():
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--lengths", default="512,4096")
     ap.add_argument("--new", type=int, default=48)
+    ap.add_argument("--cases", default="accept,round,generate")
+    ap.add_argument("--graph-out", default="profiles/spec_round_graph_bench.json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("spec_bench needs the GPU: there is nothing to time without one")
@@ -254,29 +342,36 @@ def main():
         raise SystemExit("the built library has no dta_spec_accept_draft")
     torch.manual_seed(0)
     model = D.DiffTransformer(VOCAB, 384, 6, 6, BLOCK, 0.0).to(DEV).to(torch.bfloat16).eval()
-    rows = []
+    rows, graph_rows = [], []
 
-    def keep(row):
+    def keep(row, rows=rows, out=args.out):
         rows.append(row)
         print(json.dumps(row), flush=True)
         torch.cuda.empty_cache()
-        if args.out:                                  # after every case: a run cut short keeps what it measured
-            with open(args.out, "w") as fh:
+        if out:                                       # after every case: a run cut short keeps what it measured
+            with open(out, "w") as fh:
                 json.dump(rows, fh, indent=1)
                 fh.write("\n")
 
     batches = [int(b) for b in args.batches.split(",")]
     lengths = [int(n) for n in args.lengths.split(",")]
-    for B in batches:
-        for length in lengths:
+    cases = args.cases.split(",")
+    shapes = [(B, length) for B in batches for length in lengths]
+    if "accept" in cases:
+        for B, length in shapes:
             for K in (3, 7):
                 keep(accept_case(B, length, K, args.repeats, args.warmup, 4 * args.inner))
-    for B in batches:
-        for length in lengths:
+    if "round" in cases:
+        for B, length in shapes:
             keep(round_case(model, B, length, args.repeats, args.warmup, args.inner))
-    for B in batches:
-        for length in lengths:
+    if "generate" in cases:
+        for B, length in shapes:
             keep(generate_case(model, B, length, args.new, 2))
+    if "round_graph" in cases:
+        if not ops.spec_round_supported():
+            raise SystemExit("the built library has no dta_spec_feed_rows / dta_spec_commit_lengths")
+        for B, length in shapes:
+            keep(round_graph_case(model, B, length, args.repeats, args.warmup, args.inner), graph_rows, args.graph_out)
 
 
 if __name__ == "__main__":
