@@ -21,54 +21,6 @@ _DTYPES = {torch.bfloat16: DTA_BF16, torch.float16: DTA_F16, torch.float32: DTA_
 
 ABI_VERSION = 9
 
-# every symbol include/diffattn.h declares
-EXPORTS = ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_bwd_workspace_bytes", "dta_attn_bwd_dcoef_partial_bytes",
-           "dta_ln_fwd", "dta_ln_bwd", "dta_ln_bwd_workspace_bytes",
-           "dta_rope", "dta_cast_f32", "dta_error_string", "dta_abi_version", "dta_supported",
-           "dta_attn_decode", "dta_attn_decode_workspace_bytes", "dta_swiglu_fwd", "dta_swiglu_bwd",
-           "dta_accumulate_f32", "dta_swiglu_bwd_workspace_bytes", "dta_attn_bwd_dkdv_groups",
-           "dta_attn_extend", "dta_extend_supported",
-           # ragged batches, added within ABI 9: their presence is the capability check
-           "dta_attn_decode_ragged", "dta_attn_extend_ragged",
-           # paged caches (block table over a pool of pages), added the same way
-           "dta_attn_decode_paged", "dta_attn_extend_paged",
-           # fp8 (e4m3fn) pages with per-(row, head) scales, added the same way
-           "dta_attn_decode_paged_fp8", "dta_kv_quant_rows",
-           # the multi-row step on fp8 pages, added the same way
-           "dta_attn_extend_paged_fp8", "dta_extend_fp8_supported",
-           # the split-key decode for a step of 2 .. 8 rows, added the same way
-           "dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
-           "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported",
-           # the shared-prefix decode on the paged cache, added the same way
-           "dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported",
-           # the fused row write of a ragged / paged step, added the same way
-           "dta_kv_step_rows",
-           # seeded temperature / top-k / top-p sampling of logits rows, added the same way
-           "dta_sample_rows",
-           # a speculative round's acceptance and next prompt-lookup draft, added the same way
-           "dta_spec_accept_draft",
-           # the feed and the length commit of a fixed-shape (graph-replayed) speculative round, added the same way
-           "dta_spec_feed_rows", "dta_spec_commit_lengths")
-# the entry points an older library of the same ABI may lack without being unusable
-# (``ops.fp8_cache_supported``)
-FP8_EXPORTS = ("dta_attn_decode_paged_fp8", "dta_kv_quant_rows")
-# and the later pair of the fp8 extend step (``ops.extend_fp8_supported``)
-FP8_EXTEND_EXPORTS = ("dta_attn_extend_paged_fp8", "dta_extend_fp8_supported")
-# and the split-key decode for a step of 2 .. 8 rows (``ops.decode_rows_supported``), added the same way
-ROWS_EXPORTS = ("dta_attn_decode_rows", "dta_attn_decode_rows_paged", "dta_attn_decode_rows_paged_fp8",
-                "dta_attn_decode_rows_workspace_bytes", "dta_decode_rows_supported")
-# and the shared-prefix decode on the paged cache (``ops.decode_shared_supported``), added the same way
-SHARED_EXPORTS = ("dta_attn_decode_paged_shared", "dta_attn_decode_paged_shared_fp8", "dta_decode_shared_supported")
-# and the fused row write of a ragged / paged step (``ops.kv_step_supported``), added the same way
-STEP_EXPORTS = ("dta_kv_step_rows",)
-# and the row sampler (``ops.sample_supported``), added the same way
-SAMPLE_EXPORTS = ("dta_sample_rows",)
-# and the speculative round's accept + draft kernel (``ops.spec_supported``), added the same way
-SPEC_EXPORTS = ("dta_spec_accept_draft",)
-# and the glue of the fixed-shape round (``ops.spec_round_supported``), added the same way
-SPEC_ROUND_EXPORTS = ("dta_spec_feed_rows", "dta_spec_commit_lengths")
-
-
 class DtaTensor(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p), ("sb", ctypes.c_int64), ("st", ctypes.c_int64),
                 ("sh", ctypes.c_int64), ("si", ctypes.c_int64)]
@@ -256,8 +208,86 @@ class SpecCommitLengthsArgs(ctypes.Structure):
                 + [(n, ctypes.c_void_p) for n in ("lengths", "result", "slots")])
 
 
+_I32, _I64, _VP = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+_INT, _SIZE = ctypes.c_int, ctypes.c_size_t
+
+# Every symbol include/diffattn.h declares, once: symbol -> (the argument struct of an
+# ``(args*, stream)`` entry point, or the argtypes list; restype; feature group).  A group names
+# entry points that arrived within ABI 9, each set "added the same way": an older library of the
+# same ABI may lack them without being unusable, and their presence is the capability check.
+_SYMBOLS = {
+    "dta_attn_fwd": (AttnFwdArgs, _INT, None),
+    "dta_attn_bwd": (AttnBwdArgs, _INT, None),
+    "dta_attn_bwd_workspace_bytes": ([_I32] * 5, _SIZE, None),
+    "dta_attn_bwd_dcoef_partial_bytes": ([_I32] * 4, _SIZE, None),
+    "dta_ln_fwd": (LnArgs, _INT, None),
+    "dta_ln_bwd": (LnArgs, _INT, None),
+    "dta_ln_bwd_workspace_bytes": ([_I64] * 2, _SIZE, None),
+    "dta_rope": (RopeArgs, _INT, None),
+    "dta_cast_f32": ([_I32] * 6 + [_VP, DtaTensor, _VP], _INT, None),
+    "dta_error_string": ([_INT], ctypes.c_char_p, None),
+    "dta_abi_version": ([], _INT, None),
+    "dta_supported": ([_I32] * 4, _INT, None),
+    "dta_attn_decode": (DecodeArgs, _INT, None),
+    "dta_attn_decode_workspace_bytes": ([_I32] * 6, _SIZE, None),
+    "dta_swiglu_fwd": (SwigluArgs, _INT, None),
+    "dta_swiglu_bwd": (SwigluArgs, _INT, None),
+    "dta_accumulate_f32": ([_I32, _I64, _VP, _VP, _VP], _INT, None),
+    "dta_swiglu_bwd_workspace_bytes": ([_I64, _I64], _SIZE, None),
+    "dta_attn_bwd_dkdv_groups": ([_I32] * 5, _INT, None),
+    "dta_attn_extend": (ExtendArgs, _INT, None),
+    "dta_extend_supported": ([_I32] * 4, _INT, None),
+    # ragged batches, then paged caches (block table over a pool of pages): no group, their tests need them
+    "dta_attn_decode_ragged": (DecodeRaggedArgs, _INT, None),
+    "dta_attn_extend_ragged": (ExtendRaggedArgs, _INT, None),
+    "dta_attn_decode_paged": (DecodePagedArgs, _INT, None),
+    "dta_attn_extend_paged": (ExtendPagedArgs, _INT, None),
+    # fp8 (e4m3fn) pages with per-(row, head) scales (``ops.fp8_cache_supported``)
+    "dta_attn_decode_paged_fp8": (DecodePagedFp8Args, _INT, "fp8"),
+    "dta_kv_quant_rows": (KvQuantRowsArgs, _INT, "fp8"),
+    # the multi-row step on fp8 pages (``ops.extend_fp8_supported``)
+    "dta_attn_extend_paged_fp8": (ExtendPagedFp8Args, _INT, "fp8_extend"),
+    "dta_extend_fp8_supported": ([_I32] * 4, _INT, "fp8_extend"),
+    # the split-key decode for a step of 2 .. 8 rows (``ops.decode_rows_supported``)
+    "dta_attn_decode_rows": (DecodeRowsArgs, _INT, "rows"),
+    "dta_attn_decode_rows_paged": (DecodeRowsPagedArgs, _INT, "rows"),
+    "dta_attn_decode_rows_paged_fp8": (DecodeRowsPagedFp8Args, _INT, "rows"),
+    "dta_attn_decode_rows_workspace_bytes": ([_I32] * 7, _SIZE, "rows"),
+    "dta_decode_rows_supported": ([_I32] * 6, _INT, "rows"),
+    # the shared-prefix decode on the paged cache (``ops.decode_shared_supported``)
+    "dta_attn_decode_paged_shared": (DecodePagedSharedArgs, _INT, "shared"),
+    "dta_attn_decode_paged_shared_fp8": (DecodePagedSharedFp8Args, _INT, "shared"),
+    "dta_decode_shared_supported": ([_I32] * 5, _INT, "shared"),
+    # the fused row write of a ragged / paged step (``ops.kv_step_supported``)
+    "dta_kv_step_rows": (KvStepRowsArgs, _INT, "step"),
+    # seeded temperature / top-k / top-p sampling of logits rows (``ops.sample_supported``)
+    "dta_sample_rows": (SampleRowsArgs, _INT, "sample"),
+    # a speculative round's acceptance and next prompt-lookup draft (``ops.spec_supported``)
+    "dta_spec_accept_draft": (SpecAcceptDraftArgs, _INT, "spec"),
+    # the feed and the length commit of a fixed-shape (graph-replayed) round (``ops.spec_round_supported``)
+    "dta_spec_feed_rows": (SpecFeedRowsArgs, _INT, "spec_round"),
+    "dta_spec_commit_lengths": (SpecCommitLengthsArgs, _INT, "spec_round"),
+}
+
+
+EXPORTS = tuple(_SYMBOLS)
+_GROUPS = {group: tuple(name for name, row in _SYMBOLS.items() if row[2] == group)
+           for group in dict.fromkeys(row[2] for row in _SYMBOLS.values())}
+FP8_EXPORTS = _GROUPS["fp8"]
+FP8_EXTEND_EXPORTS = _GROUPS["fp8_extend"]
+ROWS_EXPORTS = _GROUPS["rows"]
+SHARED_EXPORTS = _GROUPS["shared"]
+STEP_EXPORTS = _GROUPS["step"]
+SAMPLE_EXPORTS = _GROUPS["sample"]
+SPEC_EXPORTS = _GROUPS["spec"]
+SPEC_ROUND_EXPORTS = _GROUPS["spec_round"]
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
+
+
+def _has(lib, names) -> bool:
+    return all(hasattr(lib, name) for name in names)
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:
@@ -270,81 +300,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             raise RuntimeError(f"libdiffattn.so not found at {path}: run __graft_entry__.build() "
                                "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         lib = ctypes.CDLL(path)
-        P = ctypes.POINTER
-        lib.dta_attn_fwd.argtypes = [P(AttnFwdArgs), ctypes.c_void_p]
-        lib.dta_attn_bwd.argtypes = [P(AttnBwdArgs), ctypes.c_void_p]
-        lib.dta_ln_fwd.argtypes = [P(LnArgs), ctypes.c_void_p]
-        lib.dta_ln_bwd.argtypes = [P(LnArgs), ctypes.c_void_p]
-        lib.dta_rope.argtypes = [P(RopeArgs), ctypes.c_void_p]
-        lib.dta_swiglu_fwd.argtypes = [P(SwigluArgs), ctypes.c_void_p]
-        lib.dta_swiglu_bwd.argtypes = [P(SwigluArgs), ctypes.c_void_p]
-        lib.dta_cast_f32.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_void_p, DtaTensor, ctypes.c_void_p]
-        lib.dta_swiglu_bwd_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
-        lib.dta_swiglu_bwd_workspace_bytes.restype = ctypes.c_size_t
-        lib.dta_accumulate_f32.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p]
-        lib.dta_attn_decode.argtypes = [P(DecodeArgs), ctypes.c_void_p]
-        lib.dta_attn_decode_workspace_bytes.argtypes = [ctypes.c_int32] * 6
-        lib.dta_attn_extend.argtypes = [P(ExtendArgs), ctypes.c_void_p]
-        lib.dta_extend_supported.argtypes = [ctypes.c_int32] * 4
-        lib.dta_attn_decode_ragged.argtypes = [P(DecodeRaggedArgs), ctypes.c_void_p]
-        lib.dta_attn_extend_ragged.argtypes = [P(ExtendRaggedArgs), ctypes.c_void_p]
-        lib.dta_attn_decode_paged.argtypes = [P(DecodePagedArgs), ctypes.c_void_p]
-        lib.dta_attn_extend_paged.argtypes = [P(ExtendPagedArgs), ctypes.c_void_p]
-        lib.dta_attn_decode_workspace_bytes.restype = ctypes.c_size_t
-        lib.dta_attn_bwd_workspace_bytes.argtypes = [ctypes.c_int32] * 5
-        lib.dta_attn_bwd_workspace_bytes.restype = ctypes.c_size_t
-        lib.dta_attn_bwd_dcoef_partial_bytes.argtypes = [ctypes.c_int32] * 4
-        lib.dta_attn_bwd_dcoef_partial_bytes.restype = ctypes.c_size_t
-        lib.dta_ln_bwd_workspace_bytes.argtypes = [ctypes.c_int64] * 2
-        lib.dta_ln_bwd_workspace_bytes.restype = ctypes.c_size_t
-        lib.dta_error_string.argtypes = [ctypes.c_int]
-        lib.dta_error_string.restype = ctypes.c_char_p
-        lib.dta_supported.argtypes = [ctypes.c_int32] * 4
-        lib.dta_attn_bwd_dkdv_groups.argtypes = [ctypes.c_int32] * 5
-        for fn in ("dta_attn_fwd", "dta_attn_bwd", "dta_attn_decode", "dta_ln_fwd", "dta_ln_bwd", "dta_rope", "dta_cast_f32",
-                   "dta_abi_version", "dta_supported", "dta_swiglu_fwd", "dta_swiglu_bwd", "dta_accumulate_f32",
-                   "dta_attn_bwd_dkdv_groups", "dta_attn_extend", "dta_extend_supported", "dta_attn_decode_ragged",
-                   "dta_attn_extend_ragged", "dta_attn_decode_paged", "dta_attn_extend_paged"):
-            getattr(lib, fn).restype = ctypes.c_int
-        if fp8_symbols(lib):
-            lib.dta_attn_decode_paged_fp8.argtypes = [P(DecodePagedFp8Args), ctypes.c_void_p]
-            lib.dta_kv_quant_rows.argtypes = [P(KvQuantRowsArgs), ctypes.c_void_p]
-            lib.dta_attn_decode_paged_fp8.restype = lib.dta_kv_quant_rows.restype = ctypes.c_int
-        if fp8_extend_symbols(lib):
-            lib.dta_attn_extend_paged_fp8.argtypes = [P(ExtendPagedFp8Args), ctypes.c_void_p]
-            lib.dta_extend_fp8_supported.argtypes = [ctypes.c_int32] * 4
-            lib.dta_attn_extend_paged_fp8.restype = lib.dta_extend_fp8_supported.restype = ctypes.c_int
-        if rows_symbols(lib):
-            lib.dta_attn_decode_rows.argtypes = [P(DecodeRowsArgs), ctypes.c_void_p]
-            lib.dta_attn_decode_rows_paged.argtypes = [P(DecodeRowsPagedArgs), ctypes.c_void_p]
-            lib.dta_attn_decode_rows_paged_fp8.argtypes = [P(DecodeRowsPagedFp8Args), ctypes.c_void_p]
-            lib.dta_attn_decode_rows_workspace_bytes.argtypes = [ctypes.c_int32] * 7
-            lib.dta_attn_decode_rows_workspace_bytes.restype = ctypes.c_size_t
-            lib.dta_decode_rows_supported.argtypes = [ctypes.c_int32] * 6
-            for fn in ROWS_EXPORTS:
-                if fn != "dta_attn_decode_rows_workspace_bytes":
-                    getattr(lib, fn).restype = ctypes.c_int
-        if shared_symbols(lib):
-            lib.dta_attn_decode_paged_shared.argtypes = [P(DecodePagedSharedArgs), ctypes.c_void_p]
-            lib.dta_attn_decode_paged_shared_fp8.argtypes = [P(DecodePagedSharedFp8Args), ctypes.c_void_p]
-            lib.dta_decode_shared_supported.argtypes = [ctypes.c_int32] * 5
-            for fn in SHARED_EXPORTS:
-                getattr(lib, fn).restype = ctypes.c_int
-        if step_symbols(lib):
-            lib.dta_kv_step_rows.argtypes = [P(KvStepRowsArgs), ctypes.c_void_p]
-            lib.dta_kv_step_rows.restype = ctypes.c_int
-        if sample_symbols(lib):
-            lib.dta_sample_rows.argtypes = [P(SampleRowsArgs), ctypes.c_void_p]
-            lib.dta_sample_rows.restype = ctypes.c_int
-        if spec_symbols(lib):
-            lib.dta_spec_accept_draft.argtypes = [P(SpecAcceptDraftArgs), ctypes.c_void_p]
-            lib.dta_spec_accept_draft.restype = ctypes.c_int
-        if spec_round_symbols(lib):
-            lib.dta_spec_feed_rows.argtypes = [P(SpecFeedRowsArgs), ctypes.c_void_p]
-            lib.dta_spec_feed_rows.restype = ctypes.c_int
-            lib.dta_spec_commit_lengths.argtypes = [P(SpecCommitLengthsArgs), ctypes.c_void_p]
-            lib.dta_spec_commit_lengths.restype = ctypes.c_int
+        for group, names in _GROUPS.items():
+            if group is not None and not _has(lib, names):
+                continue                            # a feature group is typed only if the library has all of it
+            for name in names:
+                args, restype, _ = _SYMBOLS[name]
+                fn = getattr(lib, name)
+                fn.argtypes = args if isinstance(args, list) else [ctypes.POINTER(args), _VP]
+                fn.restype = restype
         if lib.dta_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffattn ABI {lib.dta_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -353,48 +316,48 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
 
 def fp8_symbols(lib) -> bool:
     """Whether ``lib`` exports the fp8-cache entry points (they arrived inside ABI 9)."""
-    return all(hasattr(lib, name) for name in FP8_EXPORTS)
+    return _has(lib, FP8_EXPORTS)
 
 
 def fp8_extend_symbols(lib) -> bool:
     """Whether ``lib`` exports the fp8 extend entry points (they arrived inside ABI 9, after the
     fp8-cache ones)."""
-    return all(hasattr(lib, name) for name in FP8_EXTEND_EXPORTS)
+    return _has(lib, FP8_EXTEND_EXPORTS)
 
 
 def rows_symbols(lib) -> bool:
     """Whether ``lib`` exports the multi-row split-key decode entry points (they arrived inside
     ABI 9, after the fp8 extend ones)."""
-    return all(hasattr(lib, name) for name in ROWS_EXPORTS)
+    return _has(lib, ROWS_EXPORTS)
 
 
 def shared_symbols(lib) -> bool:
     """Whether ``lib`` exports the shared-prefix decode entry points (they arrived inside ABI 9,
     after the multi-row decode ones)."""
-    return all(hasattr(lib, name) for name in SHARED_EXPORTS)
+    return _has(lib, SHARED_EXPORTS)
 
 
 def step_symbols(lib) -> bool:
     """Whether ``lib`` exports the fused row write of a ragged / paged step (it arrived inside ABI 9,
     after the shared-prefix decode)."""
-    return all(hasattr(lib, name) for name in STEP_EXPORTS)
+    return _has(lib, STEP_EXPORTS)
 
 
 def sample_symbols(lib) -> bool:
     """Whether ``lib`` exports the row sampler (it arrived inside ABI 9, after the fused row write)."""
-    return all(hasattr(lib, name) for name in SAMPLE_EXPORTS)
+    return _has(lib, SAMPLE_EXPORTS)
 
 
 def spec_symbols(lib) -> bool:
     """Whether ``lib`` exports the speculative round's accept + draft kernel (it arrived inside ABI 9, after
     the row sampler)."""
-    return all(hasattr(lib, name) for name in SPEC_EXPORTS)
+    return _has(lib, SPEC_EXPORTS)
 
 
 def spec_round_symbols(lib) -> bool:
     """Whether ``lib`` exports the feed and the length commit of the fixed-shape speculative round (they
     arrived inside ABI 9, after the accept + draft kernel)."""
-    return all(hasattr(lib, name) for name in SPEC_ROUND_EXPORTS)
+    return _has(lib, SPEC_ROUND_EXPORTS)
 
 
 def check(rc: int) -> None:

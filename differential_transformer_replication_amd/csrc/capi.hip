@@ -499,11 +499,19 @@ static int page_shift(int page_size) {
   }
 }
 
+// a device array of 4-byte elements (lengths, pos, count, a block table, a scale pool); NULL
+// passes only where the argument is optional
+static bool dev_i32(const void* p, bool required = true) { return (p || !required) && (uintptr_t)p % 4 == 0; }
+
+// a multi-row step's own arguments: pos required, count optional
+extern "C++" template <class A>
+static bool step_ptrs_ok(const A* a) { return dev_i32(a->pos_dev) && dev_i32(a->count_dev, false); }
+
 // The paged entry points' own arguments: a block table over a pool of n_pages pages of
 // page_size rows, max_pages entries per sequence, t_cap the logical capacity.
 extern "C++" template <class A>
 static bool page_table(const A* a, PageTable& g) {
-  if (!a->block_table_dev || (uintptr_t)a->block_table_dev % 4) return false;
+  if (!dev_i32(a->block_table_dev)) return false;
   const int shift = page_shift(a->page_size);
   if (!shift) return false;
   if (a->n_pages < 1 || a->max_pages < 1 || (int64_t)a->max_pages * a->page_size != a->t_cap) return false;
@@ -519,35 +527,65 @@ static bool ok_byte_pool(const dta_tensor& t, int width, bool with_i) {
   return t.sb >= 0 && t.st >= 0 && t.sh >= 0 && t.si >= 0;
 }
 
-// dta_attn_decode and dta_attn_decode_ragged: one validation, one launch path.  ldev / lsb:
-// the device length(s) and their batch stride (0: one value, 1: int32 [B]).
-// kc / vc: the cache views (contiguous [b][t], or with a table in pg the page pool);
-// scales: NULL, or the fp32 scale pool of an fp8 page pool (kc / vc are then byte views)
+// the fp8 entry points' own arguments, checked after the table: the scale pool, a page of it
+// that holds every (row, head, K_i | V) scale, and 16-byte page and row strides of the byte pools
 extern "C++" template <class A>
-static int decode_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const int32_t* ldev, int lsb,
-                       const PageTable& pg, void* stream, const float* scales = nullptr, int64_t scales_sb = 0) {
-  if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
-  if (a->head_size % 8 || a->head_size > 128 || a->n_terms > 4 || a->dv > 256) return DTA_ERR_UNSUPPORTED;
-  if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
-  if ((int64_t)a->B * a->H == 0) return DTA_OK;
-  // every operand is read or written by 16-byte vector accesses: full alignment checks on all four
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
-    return DTA_ERR_INVALID;
-  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
-             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
-    return DTA_ERR_INVALID;
+static bool fp8_scales_ok(const A* a) {
+  if (!dev_i32(a->scale_pool_dev)) return false;
+  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1)) return false;
+  return !(a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16);
+}
+
+// q, o, coef and the cache views kc / vc (fp8: byte views) of every decode and extend entry point:
+// each is read or written by 16-byte vector accesses (O of the extend by 8-byte ones)
+extern "C++" template <class A>
+static bool cache_operands_ok(const A* a, const dta_tensor& kc, const dta_tensor& vc, bool fp8) {
+  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef) return false;
+  return fp8 ? ok_byte_pool(kc, a->head_size, true) && ok_byte_pool(vc, a->dv, false)
+             : ok_tensor(kc, a->dtype, true) && ok_tensor(vc, a->dtype, false);
+}
+
+// What every decode launch takes, on checked operands.  kc / vc: the cache views (contiguous
+// [b][t], or with a table in pg the page pool); scales: NULL, or the fp32 scale pool of an fp8 page
+// pool; rows: query rows per (b, h); bound: the host bound of the keys, which sets the splits
+extern "C++" template <class A>
+static DecodeParams decode_params(const A* a, const dta_tensor& kc, const dta_tensor& vc, const PageTable& pg, int rows,
+                                  int bound, const float* scales, int64_t scales_sb) {
   DecodeParams p{};
   p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
   p.coef = a->coef; p.ws = a->workspace;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
-  p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = ldev; p.Lsb = lsb;
-  p.S = (int)decode_splits(a->length);
-  p.ml = a->workspace + (int64_t)a->B * a->H * p.S * a->n_terms * a->dv;   // after the partial rows
-  if (scales) {
-    p.kvs = scales; p.kvs_sb = scales_sb;
-    return status(launch_decode_f8(a->dtype, p, (hipStream_t)stream));
-  }
-  return status(launch_decode(a->dtype, p, (hipStream_t)stream));
+  p.L = bound; p.ldw = a->t_cap; p.scale = a->scale;
+  p.S = (int)decode_splits(bound);
+  p.ml = a->workspace + (int64_t)a->B * a->H * rows * p.S * a->n_terms * a->dv;   // after the partial rows
+  p.kvs = scales; p.kvs_sb = scales_sb;
+  return p;
+}
+
+// the shared-prefix plan of dta_attn_decode_paged_shared and _fp8
+struct SharedGroups { int n; const int32_t* members; const int32_t* rows; };
+
+// Every one-row decode entry point: one validation, one launch path.  ldev / lsb: the device
+// length(s) and their batch stride (0: one value, 1: int32 [B]); kc / vc / pg / scales as for
+// decode_params; sh: NULL, or the plan, whose own checks follow the dims'
+extern "C++" template <class A>
+static int decode_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const int32_t* ldev, int lsb,
+                       const PageTable& pg, void* stream, const float* scales = nullptr, int64_t scales_sb = 0,
+                       const SharedGroups* sh = nullptr) {
+  if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
+  if (sh && (sh->n < 0 || (sh->n > 0 && (!dev_i32(sh->members) || !dev_i32(sh->rows))))) return DTA_ERR_INVALID;
+  if (sh ? !decode_shared_supported(a->dtype, a->head_size, a->n_terms, a->dv)
+         : a->head_size % 8 || a->head_size > 128 || a->n_terms > 4 || a->dv > 256)
+    return DTA_ERR_UNSUPPORTED;
+  if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
+  if ((int64_t)a->B * a->H == 0) return DTA_OK;
+  if (!cache_operands_ok(a, kc, vc, scales != nullptr) || !aligned_ptr(a->workspace)) return DTA_ERR_INVALID;
+  DecodeParams p = decode_params(a, kc, vc, pg, 1, a->length, scales, scales_sb);
+  p.Ldev = ldev; p.Lsb = lsb;
+  const hipStream_t st = (hipStream_t)stream;
+  if (!sh) return status(scales ? launch_decode_f8(a->dtype, p, st) : launch_decode(a->dtype, p, st));
+  p.sh_g = sh->n; p.sh_mem = sh->members; p.sh_rows = sh->rows;
+  return status(scales ? launch_decode_shared_f8(a->dtype, p, st) : launch_decode_shared(a->dtype, p, st));
 }
 
 int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
@@ -556,23 +594,19 @@ int dta_attn_decode(const dta_attn_decode_args* a, void* stream) {
 }
 
 int dta_attn_decode_ragged(const dta_attn_decode_ragged_args* a, void* stream) {
-  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4) return DTA_ERR_INVALID;
+  if (!a || !dev_i32(a->lengths_dev)) return DTA_ERR_INVALID;
   return decode_call(a, a->k_cache, a->v_cache, a->lengths_dev, 1, PageTable{}, stream);
 }
 
 int dta_attn_decode_paged(const dta_attn_decode_paged_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
+  if (!a || !dev_i32(a->lengths_dev) || !page_table(a, pg)) return DTA_ERR_INVALID;
   return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream);
 }
 
 int dta_attn_decode_paged_fp8(const dta_attn_decode_paged_fp8_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
-  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
-  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
-    return DTA_ERR_INVALID;
-  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  if (!a || !dev_i32(a->lengths_dev) || !page_table(a, pg) || !fp8_scales_ok(a)) return DTA_ERR_INVALID;
   return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, a->scale_pool_dev, a->scale_page_stride);
 }
 
@@ -582,52 +616,19 @@ int dta_decode_shared_supported(int32_t dtype, int32_t head_size, int32_t n_term
   return decode_shared_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }
 
-// dta_attn_decode_paged_shared and _fp8: decode_call's checks of the operands, then the plan's
-extern "C++" template <class A>
-static int decode_shared_call(const A* a, const PageTable& pg, void* stream, const float* scales = nullptr,
-                              int64_t scales_sb = 0) {
-  if (!ok_dims(a->dtype, a->B, 1, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
-  if (a->n_groups < 0) return DTA_ERR_INVALID;
-  if (a->n_groups > 0 && (!a->group_members_dev || (uintptr_t)a->group_members_dev % 4 || !a->group_rows_dev ||
-                          (uintptr_t)a->group_rows_dev % 4))
-    return DTA_ERR_INVALID;
-  if (!decode_shared_supported(a->dtype, a->head_size, a->n_terms, a->dv)) return DTA_ERR_UNSUPPORTED;
-  if (a->length < 1 || a->t_cap < a->length) return DTA_ERR_INVALID;
-  if ((int64_t)a->B * a->H == 0) return DTA_OK;
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
-    return DTA_ERR_INVALID;
-  if (scales ? !ok_byte_pool(a->k_pool, a->head_size, true) || !ok_byte_pool(a->v_pool, a->dv, false)
-             : !ok_tensor(a->k_pool, a->dtype, true) || !ok_tensor(a->v_pool, a->dtype, false))
-    return DTA_ERR_INVALID;
-  DecodeParams p{};
-  p.q = t5(a->q); p.k = t5(a->k_pool); p.v = t5(a->v_pool); p.o = t5(a->o); p.pg = pg;
-  p.coef = a->coef; p.ws = a->workspace;
-  p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
-  p.L = a->length; p.ldw = a->t_cap; p.scale = a->scale; p.Ldev = a->lengths_dev; p.Lsb = 1;
-  p.S = (int)decode_splits(a->length);
-  p.ml = a->workspace + (int64_t)a->B * a->H * p.S * a->n_terms * a->dv;   // after the partial rows
-  p.sh_g = a->n_groups; p.sh_mem = a->group_members_dev; p.sh_rows = a->group_rows_dev;
-  if (scales) {
-    p.kvs = scales; p.kvs_sb = scales_sb;
-    return status(launch_decode_shared_f8(a->dtype, p, (hipStream_t)stream));
-  }
-  return status(launch_decode_shared(a->dtype, p, (hipStream_t)stream));
-}
-
 int dta_attn_decode_paged_shared(const dta_attn_decode_paged_shared_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
-  return decode_shared_call(a, pg, stream);
+  if (!a || !dev_i32(a->lengths_dev) || !page_table(a, pg)) return DTA_ERR_INVALID;
+  const SharedGroups sh{a->n_groups, a->group_members_dev, a->group_rows_dev};
+  return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, nullptr, 0, &sh);
 }
 
 int dta_attn_decode_paged_shared_fp8(const dta_attn_decode_paged_shared_fp8_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->lengths_dev || (uintptr_t)a->lengths_dev % 4 || !page_table(a, pg)) return DTA_ERR_INVALID;
-  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
-  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
-    return DTA_ERR_INVALID;
-  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
-  return decode_shared_call(a, pg, stream, a->scale_pool_dev, a->scale_page_stride);
+  if (!a || !dev_i32(a->lengths_dev) || !page_table(a, pg) || !fp8_scales_ok(a)) return DTA_ERR_INVALID;
+  const SharedGroups sh{a->n_groups, a->group_members_dev, a->group_rows_dev};
+  return decode_call(a, a->k_pool, a->v_pool, a->lengths_dev, 1, pg, stream, a->scale_pool_dev, a->scale_page_stride,
+                     &sh);
 }
 
 // ---- split-key decode for a step of 1 .. 8 rows per sequence -----------------------------------
@@ -644,35 +645,22 @@ size_t dta_attn_decode_rows_workspace_bytes(int32_t B, int32_t H, int32_t n_term
   return (size_t)B * H * Tq * decode_splits(t_cap) * n_terms * (dv + 2) * 4;
 }
 
-// dta_attn_decode_rows, _paged and _paged_fp8: one validation, one launch path (decode_call's
-// checks of the operands, extend_call's of the step)
+// dta_attn_decode_rows, _paged and _paged_fp8: the step's own checks (pos / count, the Tq range,
+// the plan), then decode_call's of the operands and its launch parameters at the capacity
 extern "C++" template <class A>
 static int decode_rows_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, const PageTable& pg, void* stream,
                             const float* scales = nullptr, int64_t scales_sb = 0) {
-  if (!a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  if (!step_ptrs_ok(a)) return DTA_ERR_INVALID;
   if (a->Tq < 1 || a->Tq > 8) return DTA_ERR_INVALID;
   if (!ok_dims(a->dtype, a->B, a->Tq, a->H, a->n_terms, a->head_size, a->dv)) return DTA_ERR_INVALID;
   if (!decode_rows_supported(a->dtype, a->head_size, a->n_terms, a->dv, a->Tq)) return DTA_ERR_UNSUPPORTED;
   if (a->t_cap < a->Tq) return DTA_ERR_INVALID;
   if ((int64_t)a->B * a->H == 0) return DTA_OK;
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef || !aligned_ptr(a->workspace))
-    return DTA_ERR_INVALID;
-  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
-             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
-    return DTA_ERR_INVALID;
-  DecodeParams p{};
-  p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
-  p.coef = a->coef; p.ws = a->workspace;
-  p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
-  p.L = a->t_cap; p.ldw = a->t_cap; p.scale = a->scale;
+  if (!cache_operands_ok(a, kc, vc, scales != nullptr) || !aligned_ptr(a->workspace)) return DTA_ERR_INVALID;
+  DecodeParams p = decode_params(a, kc, vc, pg, a->Tq, a->t_cap, scales, scales_sb);
   p.Tq = a->Tq; p.pos_dev = a->pos_dev; p.cnt_dev = a->count_dev;
-  p.S = (int)decode_splits(a->t_cap);
-  p.ml = a->workspace + (int64_t)a->B * a->H * a->Tq * p.S * a->n_terms * a->dv;   // after the partial rows
-  if (scales) {
-    p.kvs = scales; p.kvs_sb = scales_sb;
-    return status(launch_decode_rows_f8(a->dtype, p, (hipStream_t)stream));
-  }
-  return status(launch_decode_rows(a->dtype, p, (hipStream_t)stream));
+  const hipStream_t st = (hipStream_t)stream;
+  return status(scales ? launch_decode_rows_f8(a->dtype, p, st) : launch_decode_rows(a->dtype, p, st));
 }
 
 int dta_attn_decode_rows(const dta_attn_decode_rows_args* a, void* stream) {
@@ -688,11 +676,7 @@ int dta_attn_decode_rows_paged(const dta_attn_decode_rows_paged_args* a, void* s
 
 int dta_attn_decode_rows_paged_fp8(const dta_attn_decode_rows_paged_fp8_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !page_table(a, pg)) return DTA_ERR_INVALID;
-  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
-  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
-    return DTA_ERR_INVALID;
-  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  if (!a || !page_table(a, pg) || !fp8_scales_ok(a)) return DTA_ERR_INVALID;
   return decode_rows_call(a, a->k_pool, a->v_pool, pg, stream, a->scale_pool_dev, a->scale_page_stride);
 }
 
@@ -703,7 +687,7 @@ int dta_kv_quant_rows(const dta_kv_quant_rows_args* a, void* stream) {
   const int shift = page_shift(a->page_size);
   if (!shift) return DTA_ERR_INVALID;
   if (a->n_pages < 1 || ((int64_t)a->n_pages + 1) * a->page_size > INT32_MAX) return DTA_ERR_INVALID;
-  if (!a->slot_dev || (uintptr_t)a->slot_dev % 4 || !a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4 ||
+  if (!dev_i32(a->slot_dev) || !dev_i32(a->scale_pool_dev) ||
       a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
     return DTA_ERR_INVALID;
   if ((int64_t)a->B * a->Tn == 0) return DTA_OK;
@@ -723,7 +707,7 @@ int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream) {
   if (a->head_size % 8 || a->dv % 8 || a->head_size > 128 || a->dv > 256 || a->n_terms > 8) return DTA_ERR_UNSUPPORTED;
   if (a->dest < DTA_KV_STEP_CONTIGUOUS || a->dest > DTA_KV_STEP_SLOTS) return DTA_ERR_INVALID;
   if (a->t_cap < 1 || a->t_cap > (1 << 30) || a->Tn > (1 << 30)) return DTA_ERR_INVALID;
-  if (!a->pos_dev || (uintptr_t)a->pos_dev % 4 || !a->count_dev || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  if (!dev_i32(a->pos_dev) || !dev_i32(a->count_dev)) return DTA_ERR_INVALID;
   const bool slots = a->dest == DTA_KV_STEP_SLOTS;
   int shift = 0;
   if (a->dest != DTA_KV_STEP_CONTIGUOUS) {
@@ -731,8 +715,8 @@ int dta_kv_step_rows(const dta_kv_step_rows_args* a, void* stream) {
     if (!shift || a->n_pages < 1 || ((int64_t)a->n_pages + 1) * a->page_size > INT32_MAX || a->max_pages < 1 ||
         (int64_t)a->max_pages * a->page_size < a->t_cap)
       return DTA_ERR_INVALID;
-    if (!a->block_table_dev || (uintptr_t)a->block_table_dev % 4) return DTA_ERR_INVALID;
-    if (slots && (!a->slots_out_dev || (uintptr_t)a->slots_out_dev % 4)) return DTA_ERR_INVALID;
+    if (!dev_i32(a->block_table_dev)) return DTA_ERR_INVALID;
+    if (slots && !dev_i32(a->slots_out_dev)) return DTA_ERR_INVALID;
   }
   if ((int64_t)a->B * a->Tn == 0) return DTA_OK;
   // every view is read or written by 16-byte vector accesses; the views a call does not use are not looked at
@@ -837,8 +821,8 @@ int dta_extend_fp8_supported(int32_t dtype, int32_t head_size, int32_t n_terms, 
   return extend_f8_supported(dtype, head_size, n_terms, dv) ? 1 : 0;
 }
 
-// dta_attn_extend and dta_attn_extend_ragged: one validation, one launch path.
-// scales: NULL, or the fp32 scale pool of an fp8 page pool (kc / vc are then byte views)
+// Every extend entry point: one validation, one launch path.  pos: the host position of
+// dta_attn_extend; pos_dev / cnt_dev: the ragged forms'; kc / vc / pg / scales as for decode_params
 extern "C++" template <class A>
 static int extend_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, int pos, const int32_t* pos_dev,
                        const int32_t* cnt_dev, const PageTable& pg, void* stream, const float* scales = nullptr,
@@ -849,22 +833,16 @@ static int extend_call(const A* a, const dta_tensor& kc, const dta_tensor& vc, i
     return DTA_ERR_UNSUPPORTED;
   if (pos < 0 || a->t_cap < 0 || (int64_t)pos + a->Tq > a->t_cap) return DTA_ERR_INVALID;
   if (a->Tq == 0 || (int64_t)a->B * a->H == 0) return DTA_OK;
-  // every operand is read or written by 16-byte vector accesses (O by 8-byte ones)
-  if (!ok_tensor(a->q, a->dtype, true) || !ok_tensor(a->o, a->dtype, false) || !a->coef) return DTA_ERR_INVALID;
-  if (scales ? !ok_byte_pool(kc, a->head_size, true) || !ok_byte_pool(vc, a->dv, false)
-             : !ok_tensor(kc, a->dtype, true) || !ok_tensor(vc, a->dtype, false))
-    return DTA_ERR_INVALID;
+  if (!cache_operands_ok(a, kc, vc, scales != nullptr)) return DTA_ERR_INVALID;
   ExtendParams p{};
   p.q = t5(a->q); p.k = t5(kc); p.v = t5(vc); p.o = t5(a->o); p.pg = pg;
   p.coef = a->coef;
   p.B = a->B; p.H = a->H; p.N = a->n_terms; p.HS = a->head_size; p.DV = a->dv;
   p.Tq = a->Tq; p.pos = pos; p.sl2 = a->scale * kLog2e;
   p.pos_dev = pos_dev; p.cnt_dev = cnt_dev; p.cap = a->t_cap;
-  if (scales) {
-    p.kvs = scales; p.kvs_sb = scales_sb;
-    return status(launch_extend_f8(a->dtype, p, (hipStream_t)stream));
-  }
-  return status(launch_extend(a->dtype, p, (hipStream_t)stream));
+  p.kvs = scales; p.kvs_sb = scales_sb;
+  const hipStream_t st = (hipStream_t)stream;
+  return status(scales ? launch_extend_f8(a->dtype, p, st) : launch_extend(a->dtype, p, st));
 }
 
 int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
@@ -873,25 +851,19 @@ int dta_attn_extend(const dta_attn_extend_args* a, void* stream) {
 }
 
 int dta_attn_extend_ragged(const dta_attn_extend_ragged_args* a, void* stream) {
-  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4) return DTA_ERR_INVALID;
+  if (!a || !step_ptrs_ok(a)) return DTA_ERR_INVALID;
   return extend_call(a, a->k_cache, a->v_cache, 0, a->pos_dev, a->count_dev, PageTable{}, stream);
 }
 
 int dta_attn_extend_paged(const dta_attn_extend_paged_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4 || !page_table(a, pg))
-    return DTA_ERR_INVALID;
+  if (!a || !step_ptrs_ok(a) || !page_table(a, pg)) return DTA_ERR_INVALID;
   return extend_call(a, a->k_pool, a->v_pool, 0, a->pos_dev, a->count_dev, pg, stream);
 }
 
 int dta_attn_extend_paged_fp8(const dta_attn_extend_paged_fp8_args* a, void* stream) {
   PageTable pg{};
-  if (!a || !a->pos_dev || (uintptr_t)a->pos_dev % 4 || (uintptr_t)a->count_dev % 4 || !page_table(a, pg))
-    return DTA_ERR_INVALID;
-  if (!a->scale_pool_dev || (uintptr_t)a->scale_pool_dev % 4) return DTA_ERR_INVALID;
-  if (a->H > 0 && a->n_terms > 0 && a->scale_page_stride < (int64_t)a->page_size * a->H * (a->n_terms + 1))
-    return DTA_ERR_INVALID;
-  if (a->k_pool.sb % 16 || a->k_pool.st % 16 || a->v_pool.sb % 16 || a->v_pool.st % 16) return DTA_ERR_INVALID;
+  if (!a || !step_ptrs_ok(a) || !page_table(a, pg) || !fp8_scales_ok(a)) return DTA_ERR_INVALID;
   return extend_call(a, a->k_pool, a->v_pool, 0, a->pos_dev, a->count_dev, pg, stream, a->scale_pool_dev,
                      a->scale_page_stride);
 }

@@ -674,30 +674,32 @@ class RaggedKVCache(KVCache):
             self.rows[layer] = buf[:, :cap]
         return self.rows[layer]
 
+    def _views(self, layer: int, qkv, dims, bs: int):
+        """The layer's (k_rows, v_rows) views the kernels read, made on first use."""
+        H, N, hs, dv = dims
+        nq = H * N * hs
+        buf = self.layer(layer, qkv.shape[0], bs, qkv.shape[-1] - nq, qkv)
+        return buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
+
     def write_rows(self, layer: int, qkv, k_rot, dims, bs: int, tbl, pos, counts):
         """Scatter a step's new rows: the real ones to cache rows pos[b] + r, the padding to
         the spare row.  Returns the (k_rows, v_rows) views the kernels read."""
-        H, N, hs, dv = dims
-        B, Tn, W = qkv.shape
-        nq = H * N * hs
-        buf = self.layer(layer, B, bs, W - nq, qkv)
+        H, N, hs, _ = dims
+        B, Tn, _ = qkv.shape
+        kv = self._views(layer, qkv, dims, bs)
         r = torch.arange(Tn, device=qkv.device)
         real = r[None, :] < counts[:, None]
         dst = torch.where(real, pos[:, None].long() + r[None, :], bs).clamp_(max=bs)
         self.store[layer].index_put_((torch.arange(B, device=qkv.device)[:, None].expand(B, Tn), dst),
-                                     _packed_new_rows(qkv, k_rot, nq))
-        return buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
+                                     _packed_new_rows(qkv, k_rot, H * N * hs))
+        return kv
 
     def step_rows(self, layer: int, qkv, dims, bs: int, tbl, pos, counts, freqs):
         """``fused_step``: what ``_rope_rows_at`` + ``write_rows`` do, as one ``ops.kv_step_rows`` (the
         padding rows write nothing; the spare row stays untouched).  Returns (the rotated q, or None
         without RoPE; the (k_rows, v_rows) views ``write_rows`` returns)."""
-        H, N, hs, dv = dims
-        B, _, W = qkv.shape
-        nq = H * N * hs
-        buf = self.layer(layer, B, bs, W - nq, qkv)
-        kv = buf[..., :nq].unflatten(-1, (H, N, hs)), buf[..., nq:].unflatten(-1, (H, dv))
-        q_rot, _, _ = ops.kv_step_rows(*ops.split_packed(qkv, H, N, hs, dv), pos, counts, bs, freqs, dest=kv)
+        kv = self._views(layer, qkv, dims, bs)
+        q_rot, _, _ = ops.kv_step_rows(*ops.split_packed(qkv, *dims), pos, counts, bs, freqs, dest=kv)
         return q_rot, kv
 
     def decode_rows(self, kv, q, coef, tbl, lengths):
@@ -984,6 +986,12 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
     stats = spec.stats
     stats.update(rounds=0, drafted=0, accepted=0, emitted=0)
 
+    def tally(counts, m):
+        stats["rounds"] += 1
+        stats["drafted"] += sum(c - 1 for c in counts if c)
+        stats["accepted"] += sum(k - 1 for k in m if k)
+        stats["emitted"] += sum(m)
+
     def accept(tok):
         ops.spec_accept_draft(hist, hlen, remaining, draft, dcnt, tok, eos, K, spec.ngram_min if lookup else 0,
                               spec.ngram_max, bs, result)
@@ -1026,10 +1034,7 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
             else:
                 for q, n in zip(seqs, have):
                     cache._rolled_back(q, n)
-            stats["rounds"] += 1
-            stats["drafted"] += sum(c - 1 for c in counts if c)
-            stats["accepted"] += sum(k - 1 for k in m if k)
-            stats["emitted"] += sum(m)
+            tally(counts, m)
             dc = dc_next
             continue
         Tn = max(counts)
@@ -1044,10 +1049,7 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
         have = [n + k for n, k in zip(have, m)]
         if any(k < c for k, c in zip(m, counts)):
             truncate(have)
-        stats["rounds"] += 1
-        stats["drafted"] += sum(c - 1 for c in counts if c)
-        stats["accepted"] += sum(k - 1 for k in m if k)
-        stats["emitted"] += sum(m)
+        tally(counts, m)
         dc = dc_next
     ends = hlen.tolist()
     out = hist.cpu()
@@ -1304,55 +1306,57 @@ class PagedKVCache(KVCache):
             self.pool[layer], self.scale_pool[layer] = buf, sc
         return buf, sc
 
+    def _views(self, layer: int, qkv, dims):
+        """The layer's pool, made on first use, as (what a row write takes, what the kernels read): the
+        pool itself and the (k, v) views of its own pages; fp8: the (k, v, scales) views of every page, the
+        spare one included, and of its own pages."""
+        H, N, hs, dv = dims
+        nq, npg = H * N * hs, self.num_pages
+        if self.kv_dtype is None:
+            pool = self.layer_pool(layer, qkv.shape[-1] - nq, qkv)
+            return pool, (pool[:npg, :, :nq].unflatten(-1, (H, N, hs)), pool[:npg, :, nq:].unflatten(-1, (H, dv)))
+        pool, scales = self.layer_pool_fp8(layer, qkv.shape[-1] - nq, H, N, qkv.device)
+        every = (pool[..., :nq].unflatten(-1, (H, N, hs)), pool[..., nq:].unflatten(-1, (H, dv)),
+                 scales.unflatten(-1, (H, N + 1)))
+        return every, (every[0][:npg], every[1][:npg], every[2][:npg])
+
     def write_rows(self, layer: int, qkv, k_rot, dims, bs: int, tbl, pos, counts):
         """Scatter a step's new rows: the real ones to row (pos[b] + r) % P of page
         tbl[b, (pos[b] + r) // P] (``pos=None``: the prefill's, from row 0), the padding to
         the spare page -- one ``index_put_``, or on an fp8 pool one ``ops.kv_quant_rows``
         (straight from the RoPE temporary and the V slice of ``qkv``: no concatenated copy).
         Returns the pool views the kernels read: (k_pool, v_pool), fp8 (k, v, scales)."""
-        H, N, hs, dv = dims
-        B, Tn, W = qkv.shape
+        H, N, hs, _ = dims
+        B, Tn, _ = qkv.shape
         nq = H * N * hs
         P, npg = self.page_size, self.num_pages
         r = torch.arange(Tn, device=qkv.device)
         at = r[None, :].expand(B, Tn) if pos is None else pos[:, None].long() + r[None, :]
         real = (r[None, :] < counts[:, None]) & (at < bs)
         page = torch.where(real, tbl.gather(1, (at // P).clamp(max=tbl.shape[1] - 1)).long(), npg)
+        store, kv = self._views(layer, qkv, dims)
         if self.kv_dtype is None:
-            pool = self.layer_pool(layer, W - nq, qkv)
-            pool.index_put_((page, at % P), _packed_new_rows(qkv, k_rot, nq))
-            return pool[:npg, :, :nq].unflatten(-1, (H, N, hs)), pool[:npg, :, nq:].unflatten(-1, (H, dv))
-        pool, scales = self.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
-        k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
-        v_all = pool[..., nq:].unflatten(-1, (H, dv))
-        s_all = scales.unflatten(-1, (H, N + 1))
-        _, k_new, v_new = ops.split_packed(qkv, H, N, hs, dv)
-        ops.kv_quant_rows(k_new if k_rot is None else k_rot, v_new, k_all, v_all, s_all,
+            store.index_put_((page, at % P), _packed_new_rows(qkv, k_rot, nq))
+            return kv
+        _, k_new, v_new = ops.split_packed(qkv, *dims)
+        ops.kv_quant_rows(k_new if k_rot is None else k_rot, v_new, *store,
                           (page * P + at % P).to(torch.int32).flatten())
-        return k_all[:npg], v_all[:npg], s_all[:npg]
+        return kv
 
     def step_rows(self, layer: int, qkv, dims, bs: int, tbl, pos, counts, freqs):
         """``fused_step``: what ``_rope_rows_at`` + ``write_rows`` do, as one ``ops.kv_step_rows`` -- on an
         fp8 pool that launch makes the rotated K_i and the slots, and ``ops.kv_quant_rows`` runs on them
         unchanged.  The spare page is never written (fp8: only by the quantiser, with the padding rows).
         Returns (the rotated q, or None without RoPE; the pool views ``write_rows`` returns)."""
-        H, N, hs, dv = dims
-        W = qkv.shape[-1]
-        nq = H * N * hs
-        P, npg = self.page_size, self.num_pages
-        q, k_new, v_new = ops.split_packed(qkv, H, N, hs, dv)
+        q, k_new, v_new = ops.split_packed(qkv, *dims)
+        store, kv = self._views(layer, qkv, dims)
         if self.kv_dtype is None:
-            pool = self.layer_pool(layer, W - nq, qkv)
-            kv = pool[:npg, :, :nq].unflatten(-1, (H, N, hs)), pool[:npg, :, nq:].unflatten(-1, (H, dv))
             q_rot, _, _ = ops.kv_step_rows(q, k_new, v_new, pos, counts, bs, freqs, dest=kv, block_table=tbl)
             return q_rot, kv
-        pool, scales = self.layer_pool_fp8(layer, W - nq, H, N, qkv.device)
-        k_all = pool[..., :nq].unflatten(-1, (H, N, hs))
-        v_all = pool[..., nq:].unflatten(-1, (H, dv))
-        s_all = scales.unflatten(-1, (H, N + 1))
-        q_rot, k_out, slots = ops.kv_step_rows(q, k_new, v_new, pos, counts, bs, freqs, None, tbl, P, npg)
-        ops.kv_quant_rows(k_new if k_out is None else k_out, v_new, k_all, v_all, s_all, slots)
-        return q_rot, (k_all[:npg], v_all[:npg], s_all[:npg])
+        q_rot, k_out, slots = ops.kv_step_rows(q, k_new, v_new, pos, counts, bs, freqs, None, tbl, self.page_size,
+                                               self.num_pages)
+        ops.kv_quant_rows(k_new if k_out is None else k_out, v_new, *store, slots)
+        return q_rot, kv
 
     def decode_rows(self, kv, q, coef, tbl, lengths):
         plan = self.shared_plan                   # set by decode_paged for its one-row step only

@@ -721,6 +721,51 @@ def _decode(lib, q: Tensor, k: Tensor, v: Tensor, coef: Tensor, bound: int, T_ca
     return o.view(B, H * dv)
 
 
+def _cache_shapes(q: Tensor, k_cache: Tensor, v_cache: Tensor) -> int:
+    """Shapes of contiguous cache views against q (B, [Tq,] H, N, hs); returns T_cap."""
+    B, (H, N, hs) = q.shape[0], q.shape[-3:]
+    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
+    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
+        raise RuntimeError("k_cache/v_cache shapes do not match q")
+    return T_cap
+
+
+def _cache_dtype(q: Tensor, k_cache: Tensor, v_cache: Tensor) -> None:
+    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
+        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+
+
+def _coef_shape(coef: Tensor, H: int, N: int) -> None:
+    if tuple(coef.shape) != (H, N):
+        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+
+
+def _batch_int32(t: Tensor, B: int, like: Tensor, name: str) -> None:
+    if not isinstance(t, Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != like.device:
+        raise RuntimeError(f"{name} must be a device int32 tensor of shape ({B},) on {like.device}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+
+
+def _decode_bound(max_length: Optional[int], T_cap: int) -> int:
+    """The host upper bound of every length of a ragged decode; default T_cap."""
+    max_length = T_cap if max_length is None else int(max_length)
+    if not 1 <= max_length <= T_cap:
+        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
+    return max_length
+
+
+def _step_operands(q: Tensor, coef: Tensor, pos: Tensor, counts: Optional[Tensor], T_cap: int, owner: str) -> None:
+    """coef, pos / counts and Tq of a ragged multi-row step against the ``owner``'s (cache's, table's) T_cap."""
+    B, Tq, H, N, _ = q.shape
+    _coef_shape(coef, H, N)
+    _batch_int32(pos, B, q, "pos")
+    if counts is not None:
+        _batch_int32(counts, B, q, "counts")
+    if Tq > T_cap:
+        raise RuntimeError(f"{Tq} new rows do not fit the {owner}'s {T_cap} rows")
+
+
 def diff_attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, length: int,
                           length_dev: Optional[Tensor] = None) -> Tensor:
     """One new query row per (b, h) against the first ``length`` cached keys:
@@ -737,13 +782,10 @@ def diff_attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
     lib = _lib.load()
     _require_gpu(q, k_cache, v_cache, coef)
     B, H, N, hs = q.shape
-    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
-    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
-        raise RuntimeError("k_cache/v_cache shapes do not match q")
+    T_cap = _cache_shapes(q, k_cache, v_cache)
     if not 1 <= length <= T_cap:
         raise RuntimeError(f"decode length {length} outside [1, {T_cap}]")
-    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
-        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+    _cache_dtype(q, k_cache, v_cache)
     if length_dev is not None:
         _require_gpu(length_dev)
         if length_dev.dtype != torch.int32 or length_dev.numel() != 1:
@@ -850,13 +892,9 @@ def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
     if q.dim() != 5:
         raise RuntimeError("q must be (B, Tq, H, N, hs)")
     B, Tq, H, N, hs = q.shape
-    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
-    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
-        raise RuntimeError("k_cache/v_cache shapes do not match q")
-    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
-        raise RuntimeError("q, k_cache and v_cache must share a dtype")
-    if tuple(coef.shape) != (H, N):
-        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
+    T_cap = _cache_shapes(q, k_cache, v_cache)
+    _cache_dtype(q, k_cache, v_cache)
+    _coef_shape(coef, H, N)
     pos = int(pos)
     if pos < 0 or pos + Tq > T_cap:
         raise RuntimeError(f"extend rows {pos}..{pos + Tq - 1} outside the cache's {T_cap} rows")
@@ -864,13 +902,6 @@ def diff_attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Ten
 
 
 # ------------------------------------------------------------------ ragged ---
-def _batch_int32(t: Tensor, B: int, like: Tensor, name: str) -> None:
-    if not isinstance(t, Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != like.device:
-        raise RuntimeError(f"{name} must be a device int32 tensor of shape ({B},) on {like.device}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be contiguous")
-
-
 def diff_attention_decode_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, coef: Tensor, lengths: Tensor,
                                  max_length: Optional[int] = None) -> Tensor:
     """``diff_attention_decode`` for a batch whose sequences sit at different lengths:
@@ -885,14 +916,9 @@ def diff_attention_decode_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
     lib = _lib.load()
     _require_gpu(q, k_cache, v_cache, coef)
     B, H, N, hs = q.shape
-    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
-    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
-        raise RuntimeError("k_cache/v_cache shapes do not match q")
-    max_length = T_cap if max_length is None else int(max_length)
-    if not 1 <= max_length <= T_cap:
-        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
-    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
-        raise RuntimeError("q, k_cache and v_cache must share a dtype")
+    T_cap = _cache_shapes(q, k_cache, v_cache)
+    max_length = _decode_bound(max_length, T_cap)
+    _cache_dtype(q, k_cache, v_cache)
     _batch_int32(lengths, B, q, "lengths")
     return _decode(lib, q, k_cache, v_cache, coef, max_length, T_cap, lengths=lengths)
 
@@ -916,18 +942,9 @@ def diff_attention_extend_ragged(q: Tensor, k_cache: Tensor, v_cache: Tensor, co
     if q.dim() != 5:
         raise RuntimeError("q must be (B, Tq, H, N, hs)")
     B, Tq, H, N, hs = q.shape
-    T_cap, dv = k_cache.shape[1], v_cache.shape[-1]
-    if tuple(k_cache.shape) != (B, T_cap, H, N, hs) or tuple(v_cache.shape) != (B, T_cap, H, dv):
-        raise RuntimeError("k_cache/v_cache shapes do not match q")
-    if q.dtype != k_cache.dtype or q.dtype != v_cache.dtype:
-        raise RuntimeError("q, k_cache and v_cache must share a dtype")
-    if tuple(coef.shape) != (H, N):
-        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
-    _batch_int32(pos, B, q, "pos")
-    if counts is not None:
-        _batch_int32(counts, B, q, "counts")
-    if Tq > T_cap:
-        raise RuntimeError(f"{Tq} new rows do not fit the cache's {T_cap} rows")
+    T_cap = _cache_shapes(q, k_cache, v_cache)
+    _cache_dtype(q, k_cache, v_cache)
+    _step_operands(q, coef, pos, counts, T_cap, "cache")
     return _extend(lib, q, k_cache, v_cache, coef, T_cap, pos_dev=pos, counts=counts, rows=_rows)
 
 
@@ -945,20 +962,55 @@ def _table_pages(block_table: Tensor, B: int, q: Tensor) -> int:
     return block_table.shape[1]
 
 
-def _paged_views(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, B: int, H: int, N: int, hs: int):
-    """Checks shared by the two paged ops; returns (n_pages, P, max_pages, dv)."""
-    if k_pool.dim() != 5 or v_pool.dim() != 4:
-        raise RuntimeError("k_pool must be (n_pages, P, H, N, hs) and v_pool (n_pages, P, H, dv)")
-    n_pages, P, dv = k_pool.shape[0], k_pool.shape[1], v_pool.shape[-1]
-    if P not in PAGE_SIZES:
-        raise RuntimeError(f"page size {P} is not one of {PAGE_SIZES}")
-    if n_pages < 1:
-        raise RuntimeError("the pool holds no page")
-    if tuple(k_pool.shape) != (n_pages, P, H, N, hs) or tuple(v_pool.shape) != (n_pages, P, H, dv):
-        raise RuntimeError("k_pool/v_pool shapes do not match q")
-    if q.dtype != k_pool.dtype or q.dtype != v_pool.dtype:
-        raise RuntimeError("q, k_pool and v_pool must share a dtype")
-    return n_pages, P, _table_pages(block_table, B, q), dv
+def _page_tuple(q: Tensor, k_pool: Tensor, v_pool: Tensor, scale_pool: Optional[Tensor], block_table: Tensor):
+    """Checks of the pool views (``scale_pool`` given: the fp8 ones, ``_fp8_views``) against q
+    (B, [Tq,] H, N, hs) and of the block table, shared by every paged op.  Returns ``_decode`` /
+    ``_extend``'s ``page`` = (block_table, P, max_pages, n_pages), T_cap and dv."""
+    B, (H, N, hs) = q.shape[0], tuple(q.shape[-3:])
+    if scale_pool is not None:
+        n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool, v_pool, scale_pool)
+        if (Hp, Np, hsp) != (H, N, hs) or k_pool.device != q.device:
+            raise RuntimeError("the pool views do not match q")
+    else:
+        if k_pool.dim() != 5 or v_pool.dim() != 4:
+            raise RuntimeError("k_pool must be (n_pages, P, H, N, hs) and v_pool (n_pages, P, H, dv)")
+        n_pages, P, dv = k_pool.shape[0], k_pool.shape[1], v_pool.shape[-1]
+        if P not in PAGE_SIZES:
+            raise RuntimeError(f"page size {P} is not one of {PAGE_SIZES}")
+        if n_pages < 1:
+            raise RuntimeError("the pool holds no page")
+        if tuple(k_pool.shape) != (n_pages, P, H, N, hs) or tuple(v_pool.shape) != (n_pages, P, H, dv):
+            raise RuntimeError("k_pool/v_pool shapes do not match q")
+        if q.dtype != k_pool.dtype or q.dtype != v_pool.dtype:
+            raise RuntimeError("q, k_pool and v_pool must share a dtype")
+    max_pages = _table_pages(block_table, B, q)
+    return (block_table, P, max_pages, n_pages), max_pages * P, dv
+
+
+def _decode_paged(lib, q: Tensor, k_pool: Tensor, v_pool: Tensor, scale_pool: Optional[Tensor], coef: Tensor,
+                  block_table: Tensor, lengths: Tensor, max_length: Optional[int], plan=None) -> Tensor:
+    """The body of the four paged decode ops (``scale_pool``: the fp8 ones; ``plan``: the shared-prefix
+    ones, checked by their caller), after their own library and device checks."""
+    B, H = q.shape[:2]
+    page, T_cap, dv = _page_tuple(q, k_pool, v_pool, scale_pool, block_table)
+    max_length = _decode_bound(max_length, T_cap)
+    _batch_int32(lengths, B, q, "lengths")
+    if plan is not None and B == 0:
+        return q.new_empty(0, H * dv)            # an empty batch (its tensors have no address to pass)
+    return _decode(lib, q, k_pool, v_pool, coef, max_length, T_cap, lengths=lengths, page=page,
+                   scale_pool=scale_pool, plan=plan)
+
+
+def _extend_paged(lib, q: Tensor, k_pool: Tensor, v_pool: Tensor, scale_pool: Optional[Tensor], coef: Tensor,
+                  block_table: Tensor, pos: Tensor, counts: Optional[Tensor], rows: bool) -> Tensor:
+    """The body of the paged extend ops and, with ``rows``, of the paged multi-row decode ops
+    (``scale_pool``: the fp8 ones), after their own library and device checks."""
+    if q.dim() != 5:
+        raise RuntimeError("q must be (B, Tq, H, N, hs)")
+    page, T_cap, _ = _page_tuple(q, k_pool, v_pool, scale_pool, block_table)
+    _step_operands(q, coef, pos, counts, T_cap, "table")
+    return _extend(lib, q, k_pool, v_pool, coef, T_cap, pos_dev=pos, counts=counts, page=page,
+                   scale_pool=scale_pool, rows=rows)
 
 
 def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
@@ -978,14 +1030,7 @@ def diff_attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
     lib = _lib.load()
     _require_gpu(q, k_pool, v_pool, coef)
     B, H, N, hs = q.shape
-    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
-    T_cap = max_pages * P
-    max_length = T_cap if max_length is None else int(max_length)
-    if not 1 <= max_length <= T_cap:
-        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
-    _batch_int32(lengths, B, q, "lengths")
-    return _decode(lib, q, k_pool, v_pool, coef, max_length, T_cap, lengths=lengths,
-                   page=(block_table, P, max_pages, n_pages))
+    return _decode_paged(lib, q, k_pool, v_pool, None, coef, block_table, lengths, max_length)
 
 
 def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef: Tensor, block_table: Tensor,
@@ -1000,20 +1045,7 @@ def diff_attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, coef:
     without a kernel plan (``extend_supported``)."""
     lib = _lib.load()
     _require_gpu(q, k_pool, v_pool, coef)
-    if q.dim() != 5:
-        raise RuntimeError("q must be (B, Tq, H, N, hs)")
-    B, Tq, H, N, hs = q.shape
-    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
-    T_cap = max_pages * P
-    if tuple(coef.shape) != (H, N):
-        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
-    _batch_int32(pos, B, q, "pos")
-    if counts is not None:
-        _batch_int32(counts, B, q, "counts")
-    if Tq > T_cap:
-        raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
-    return _extend(lib, q, k_pool, v_pool, coef, T_cap, pos_dev=pos, counts=counts,
-                   page=(block_table, P, max_pages, n_pages), rows=_rows)
+    return _extend_paged(lib, q, k_pool, v_pool, None, coef, block_table, pos, counts, _rows)
 
 
 # --------------------------------------------------------------- fp8 pages ---
@@ -1100,17 +1132,7 @@ def diff_attention_decode_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
         raise RuntimeError("this libdiffattn.so has no fp8-cache entry points (fp8_cache_supported)")
     _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
     B, H, N, hs = q.shape
-    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
-    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
-        raise RuntimeError("the pool views do not match q")
-    max_pages = _table_pages(block_table, B, q)
-    T_cap = max_pages * P
-    max_length = T_cap if max_length is None else int(max_length)
-    if not 1 <= max_length <= T_cap:
-        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
-    _batch_int32(lengths, B, q, "lengths")
-    return _decode(lib, q, k_pool_u8, v_pool_u8, coef, max_length, T_cap, lengths=lengths,
-                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool)
+    return _decode_paged(lib, q, k_pool_u8, v_pool_u8, scale_pool, coef, block_table, lengths, max_length)
 
 
 def extend_fp8_supported(dtype: torch.dtype, hs: int, N: int, dv: int) -> bool:
@@ -1141,23 +1163,7 @@ def diff_attention_extend_paged_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Ten
     if not _rows and not _lib.fp8_extend_symbols(lib):
         raise RuntimeError("this libdiffattn.so has no fp8 extend entry points (extend_fp8_supported)")
     _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
-    if q.dim() != 5:
-        raise RuntimeError("q must be (B, Tq, H, N, hs)")
-    B, Tq, H, N, hs = q.shape
-    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
-    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
-        raise RuntimeError("the pool views do not match q")
-    max_pages = _table_pages(block_table, B, q)
-    T_cap = max_pages * P
-    if tuple(coef.shape) != (H, N):
-        raise RuntimeError(f"coef must be (H, N) = ({H}, {N})")
-    _batch_int32(pos, B, q, "pos")
-    if counts is not None:
-        _batch_int32(counts, B, q, "counts")
-    if Tq > T_cap:
-        raise RuntimeError(f"{Tq} new rows do not fit the table's {T_cap} rows")
-    return _extend(lib, q, k_pool_u8, v_pool_u8, coef, T_cap, pos_dev=pos, counts=counts,
-                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool, rows=_rows)
+    return _extend_paged(lib, q, k_pool_u8, v_pool_u8, scale_pool, coef, block_table, pos, counts, _rows)
 
 
 # ------------------------------------------------- short multi-row steps ---
@@ -1897,16 +1903,7 @@ def diff_attention_decode_paged_shared(q: Tensor, k_pool: Tensor, v_pool: Tensor
     _require_gpu(q, k_pool, v_pool, coef)
     B, H, N, hs = q.shape
     _shared_plan(lib, plan, B, q)
-    n_pages, P, max_pages, dv = _paged_views(q, k_pool, v_pool, block_table, B, H, N, hs)
-    T_cap = max_pages * P
-    max_length = T_cap if max_length is None else int(max_length)
-    if not 1 <= max_length <= T_cap:
-        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
-    _batch_int32(lengths, B, q, "lengths")
-    if B == 0:
-        return q.new_empty(0, H * dv)            # an empty batch (its tensors have no address to pass)
-    return _decode(lib, q, k_pool, v_pool, coef, max_length, T_cap, lengths=lengths,
-                   page=(block_table, P, max_pages, n_pages), plan=plan)
+    return _decode_paged(lib, q, k_pool, v_pool, None, coef, block_table, lengths, max_length, plan)
 
 
 def diff_attention_decode_paged_shared_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_u8: Tensor, scale_pool: Tensor,
@@ -1918,16 +1915,4 @@ def diff_attention_decode_paged_shared_fp8(q: Tensor, k_pool_u8: Tensor, v_pool_
     _require_gpu(q, k_pool_u8, v_pool_u8, scale_pool, coef)
     B, H, N, hs = q.shape
     _shared_plan(lib, plan, B, q)
-    n_pages, P, Hp, Np, hsp, dv = _fp8_views(k_pool_u8, v_pool_u8, scale_pool)
-    if (Hp, Np, hsp) != (H, N, hs) or k_pool_u8.device != q.device:
-        raise RuntimeError("the pool views do not match q")
-    max_pages = _table_pages(block_table, B, q)
-    T_cap = max_pages * P
-    max_length = T_cap if max_length is None else int(max_length)
-    if not 1 <= max_length <= T_cap:
-        raise RuntimeError(f"decode max_length {max_length} outside [1, {T_cap}]")
-    _batch_int32(lengths, B, q, "lengths")
-    if B == 0:
-        return q.new_empty(0, H * dv)
-    return _decode(lib, q, k_pool_u8, v_pool_u8, coef, max_length, T_cap, lengths=lengths,
-                   page=(block_table, P, max_pages, n_pages), scale_pool=scale_pool, plan=plan)
+    return _decode_paged(lib, q, k_pool_u8, v_pool_u8, scale_pool, coef, block_table, lengths, max_length, plan)
