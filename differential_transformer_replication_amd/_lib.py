@@ -189,6 +189,19 @@ class SampleRowsArgs(ctypes.Structure):
                 ("token_out", ctypes.c_void_p), ("logprob_out", ctypes.c_void_p)]
 
 
+class PenalizeRowsArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("dtype", "B", "Tn", "V", "cap", "K")]
+                + [("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64),
+                   ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64),
+                   ("hist", ctypes.c_void_p), ("hist_stride", ctypes.c_int64),
+                   ("hlen_dev", ctypes.c_void_p), ("gen_start_dev", ctypes.c_void_p),
+                   ("draft", ctypes.c_void_p), ("draft_stride", ctypes.c_int64), ("dcnt_dev", ctypes.c_void_p)]
+                + [(n, ctypes.c_float) for n in ("repetition", "frequency", "presence", "floor_gap")]
+                + [(n, ctypes.c_void_p) for n in ("repetition_dev", "frequency_dev", "presence_dev", "floor_gap_dev",
+                                                  "bias")]
+                + [("bias_stride", ctypes.c_int64), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)])
+
+
 class SpecAcceptDraftArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_int32) for n in ("B", "Tn", "K", "cap", "t_cap", "ngram_min", "ngram_max", "eos_id")]
                 + [(n, ctypes.c_int64) for n in ("hist_stride", "draft_stride", "tok_stride")]
@@ -262,6 +275,9 @@ _SYMBOLS = {
     "dta_kv_step_rows": (KvStepRowsArgs, _INT, "step"),
     # seeded temperature / top-k / top-p sampling of logits rows (``ops.sample_supported``)
     "dta_sample_rows": (SampleRowsArgs, _INT, "sample"),
+    # penalties, logit bias and the min-p floor of logits rows (``ops.penalize_rows_supported``)
+    "dta_penalize_rows": (PenalizeRowsArgs, _INT, "penalty"),
+    "dta_penalize_rows_workspace_bytes": ([_I64, _I32], _SIZE, "penalty"),
     # a speculative round's acceptance and next prompt-lookup draft (``ops.spec_supported``)
     "dta_spec_accept_draft": (SpecAcceptDraftArgs, _INT, "spec"),
     # the feed and the length commit of a fixed-shape (graph-replayed) round (``ops.spec_round_supported``)
@@ -279,6 +295,7 @@ ROWS_EXPORTS = _GROUPS["rows"]
 SHARED_EXPORTS = _GROUPS["shared"]
 STEP_EXPORTS = _GROUPS["step"]
 SAMPLE_EXPORTS = _GROUPS["sample"]
+PENALTY_EXPORTS = _GROUPS["penalty"]
 SPEC_EXPORTS = _GROUPS["spec"]
 SPEC_ROUND_EXPORTS = _GROUPS["spec_round"]
 
@@ -346,6 +363,12 @@ def step_symbols(lib) -> bool:
 def sample_symbols(lib) -> bool:
     """Whether ``lib`` exports the row sampler (it arrived inside ABI 9, after the fused row write)."""
     return _has(lib, SAMPLE_EXPORTS)
+
+
+def penalty_symbols(lib) -> bool:
+    """Whether ``lib`` exports the penalty row kernel (it arrived inside ABI 9, after the fixed-shape
+    speculative round)."""
+    return _has(lib, PENALTY_EXPORTS)
 
 
 def spec_symbols(lib) -> bool:

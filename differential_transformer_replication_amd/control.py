@@ -189,12 +189,12 @@ class StandardTransformer(nn.Module):
         return logits, loss
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, prefill_chunk=None, sampler=None):
+    def generate(self, idx, max_new_tokens, prefill_chunk=None, sampler=None, penalties=None):
         kv_cache.check_prefill_chunk(prefill_chunk)      # bounds the prompt's prefill (cached path only)
         if kv_cache.enabled(idx, self):                  # KV-cache decode
-            return kv_cache.cached_generate(self, idx, max_new_tokens, prefill_chunk, sampler)
-        if sampler is not None:                          # kv_cache.Sampler: one ops.sample_rows launch per token
-            return kv_cache.naive_generate(self, idx, max_new_tokens, sampler)
+            return kv_cache.cached_generate(self, idx, max_new_tokens, prefill_chunk, sampler, penalties)
+        if sampler is not None or penalties is not None:  # kv_cache.Sampler / Penalties: one launch each per token
+            return kv_cache.naive_generate(self, idx, max_new_tokens, sampler, penalties)
         for _ in range(max_new_tokens):
             logits, _ = self(idx[:, -self.block_size:])
             probs = F.softmax(logits[:, -1, :], dim=-1)

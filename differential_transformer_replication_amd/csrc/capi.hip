@@ -758,6 +758,43 @@ int dta_sample_rows(const dta_sample_rows_args* a, void* stream) {
   return status(launch_sample(a->dtype, p, (hipStream_t)stream));
 }
 
+size_t dta_penalize_rows_workspace_bytes(int64_t R, int32_t V) {
+  if (R < 0 || V < 1 || V > (1 << 20)) return 0;
+  return penalize_workspace_bytes(R, V);
+}
+
+int dta_penalize_rows(const dta_penalize_rows_args* a, void* stream) {
+  if (!a || a->dtype < DTA_BF16 || a->dtype > DTA_F32 || a->B < 0 || a->Tn < 0 || a->V < 1) return DTA_ERR_INVALID;
+  const int64_t R = (int64_t)a->B * a->Tn;
+  if (R > INT32_MAX || a->cap < 1 || a->cap > (1 << 30) || a->K < 0 || a->K > 7) return DTA_ERR_INVALID;
+  if (a->row_stride < a->V || a->out_stride < a->V || a->hist_stride < a->cap) return DTA_ERR_INVALID;
+  if ((a->draft == nullptr) != (a->dcnt_dev == nullptr) || (a->draft && a->draft_stride < a->K)) return DTA_ERR_INVALID;
+  if (a->bias && a->bias_stride != 0 && a->bias_stride < a->V) return DTA_ERR_INVALID;
+  if (nan_bits(a->repetition) || nan_bits(a->frequency) || nan_bits(a->presence) || nan_bits(a->floor_gap) ||
+      a->repetition <= 0.f)
+    return DTA_ERR_INVALID;
+  if (!dev_i32(a->out, false) || !dev_i32(a->hist, false) || !dev_i32(a->hlen_dev, false) ||
+      !dev_i32(a->gen_start_dev, false) || !dev_i32(a->draft, false) || !dev_i32(a->dcnt_dev, false) ||
+      !dev_i32(a->repetition_dev, false) || !dev_i32(a->frequency_dev, false) || !dev_i32(a->presence_dev, false) ||
+      !dev_i32(a->floor_gap_dev, false) || !dev_i32(a->bias, false) || !dev_i32(a->workspace, false) ||
+      (uintptr_t)a->logits % esize(a->dtype))
+    return DTA_ERR_INVALID;
+  if (a->V > (1 << 20)) return DTA_ERR_UNSUPPORTED;
+  if (R == 0) return DTA_OK;
+  if (!a->logits || !a->out || !a->hist || !a->hlen_dev) return DTA_ERR_INVALID;
+  const size_t need = penalize_workspace_bytes(R, a->V);
+  if (need && (!a->workspace || a->workspace_bytes < need)) return DTA_ERR_INVALID;
+  PenaltyParams p{};
+  p.logits = a->logits; p.out = a->out; p.stride = a->row_stride; p.out_stride = a->out_stride;
+  p.hist = a->hist; p.hlen = a->hlen_dev; p.gen_start = a->gen_start_dev; p.draft = a->draft; p.dcnt = a->dcnt_dev;
+  p.hist_stride = a->hist_stride; p.draft_stride = a->draft_stride;
+  p.theta = a->repetition; p.freq = a->frequency; p.pres = a->presence; p.gap = a->floor_gap;
+  p.theta_dev = a->repetition_dev; p.freq_dev = a->frequency_dev; p.pres_dev = a->presence_dev; p.gap_dev = a->floor_gap_dev;
+  p.bias = a->bias; p.bias_stride = a->bias_stride; p.ws = need ? static_cast<uint32_t*>(a->workspace) : nullptr;
+  p.R = (int)R; p.Tn = a->Tn; p.V = a->V; p.cap = a->cap; p.K = a->K;
+  return status(launch_penalize(a->dtype, p, (hipStream_t)stream));
+}
+
 int dta_spec_accept_draft(const dta_spec_accept_draft_args* a, void* stream) {
   if (!a || a->B < 0 || a->K < 1 || a->K > 7 || a->Tn < 0 || a->Tn > a->K + 1) return DTA_ERR_INVALID;
   if (a->ngram_min < 0 || a->ngram_min > a->ngram_max || a->ngram_max < 1 || a->ngram_max > 8) return DTA_ERR_INVALID;

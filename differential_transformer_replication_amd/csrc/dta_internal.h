@@ -203,6 +203,27 @@ struct SampleParams {
 };
 int launch_sample(int dtype, const SampleParams& p, hipStream_t st);
 
+// dta_penalize_rows (penalty.hip): penalties, bias and the min-p floor of logits rows into fp32 rows
+struct PenaltyParams {
+  const void* logits;  // [R][V] in the launch's dtype, row stride in elements
+  float* out;          // [R][V] fp32
+  int64_t stride, out_stride;
+  const int* hist;     // [B][cap], row stride in elements
+  const int* hlen;     // [B], clamped to [0, cap]
+  const int* gen_start;  // [B] or NULL: 0; clamped to [0, hlen]
+  const int* draft;    // [B][K] or NULL
+  const int* dcnt;     // [B] with draft, clamped to [0, K]
+  int64_t hist_stride, draft_stride;
+  float theta, freq, pres, gap;                // used where the per-sequence pointer is NULL
+  const float* theta_dev; const float* freq_dev; const float* pres_dev; const float* gap_dev;
+  const float* bias;   // [B][V] or, bias_stride 0, [V]; or NULL
+  int64_t bias_stride;
+  uint32_t* ws;        // [R][V] where V is past the LDS table, not read before it is written
+  int R, Tn, V, cap, K;
+};
+int launch_penalize(int dtype, const PenaltyParams& p, hipStream_t st);
+size_t penalize_workspace_bytes(int64_t R, int64_t V);
+
 // dta_spec_accept_draft (spec.hip): a speculative round's acceptance, history append and next n-gram draft
 struct SpecParams {
   int* hist;           // [B][cap], row stride in elements

@@ -61,6 +61,7 @@ lengths back on the device, so the host only grows pages before the replay and r
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -73,7 +74,7 @@ from ._compat import mha_out_scale
 __all__ = ["KVCache", "DecodeGraph", "DevicePosition", "cached_generate", "enabled", "append_logits",
            "prefill_logits", "check_prefill_chunk", "RaggedKVCache", "prefill_ragged", "decode_ragged",
            "append_ragged", "generate_ragged", "PagedKVCache", "OutOfPages", "prefill_paged", "decode_paged",
-           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler", "Speculation", "SpecRound"]
+           "append_paged", "generate_paged", "SeqDecodeGraph", "Sampler", "Speculation", "SpecRound", "Penalties"]
 
 
 class Sampler:
@@ -106,6 +107,116 @@ class Sampler:
         out = ops.sample_rows(logits, self.temperature, self.top_k, self.top_p, self.seed, streams, offset,
                               return_logprobs)
         return (out[0][:, None], out[1]) if return_logprobs else out[:, None]
+
+
+class Penalties:
+    """Opt-in logit processing of the generate loops, applied before the ``Sampler`` in one
+    ``ops.penalize_rows`` launch per step (include/diffattn.h, "Sampling penalties"): ``repetition`` (> 0;
+    1: off) divides the positive and multiplies the other logits of every token the sequence holds, prompt
+    included; ``frequency`` times a token's count among the generated tokens and ``presence`` once are
+    subtracted; ``logit_bias`` -- a ``{token: float}`` dict or a (V,) tensor -- is added and ``banned`` tokens
+    get ``-inf``; ``min_p`` in [0, 1) removes what is less probable than ``min_p`` times the most probable token
+    (after the temperature; off at temperature <= 0).  The history a row is penalised with is its own
+    sequence's, so a sequence's tokens still do not depend on the batch, and a speculative round penalises
+    row j with the j drafted tokens before it: ``speculate`` emits the same tokens.  Immutable."""
+    __slots__ = ("repetition", "presence", "frequency", "min_p", "logit_bias", "banned")
+
+    def __init__(self, repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0, min_p: float = 0.0,
+                 logit_bias=None, banned=()):
+        repetition, presence, frequency, min_p = float(repetition), float(presence), float(frequency), float(min_p)
+        inf = float("inf")
+        if not 0 < repetition < inf:
+            raise ValueError(f"repetition {repetition} must be positive and finite")
+        if not (-inf < presence < inf and -inf < frequency < inf):
+            raise ValueError("presence and frequency must be finite")
+        if not 0 <= min_p < 1:
+            raise ValueError(f"min_p {min_p} outside [0, 1)")
+        if isinstance(logit_bias, dict):
+            logit_bias = {int(t): float(v) for t, v in logit_bias.items()}
+            if any(t < 0 or v != v or v == inf for t, v in logit_bias.items()):
+                raise ValueError("logit_bias maps token ids >= 0 to values that are neither NaN nor +inf")
+        elif isinstance(logit_bias, torch.Tensor):
+            if logit_bias.dim() != 1 or not logit_bias.is_floating_point() or bool(torch.isnan(logit_bias).any()) \
+                    or bool((logit_bias == inf).any()):
+                raise ValueError("a logit_bias tensor is (V,), floating point, without NaN or +inf")
+            logit_bias = logit_bias.detach().clone()
+        elif logit_bias is not None:
+            raise ValueError("logit_bias must be a {token: float} dict or a (V,) tensor")
+        banned = tuple(sorted({int(t) for t in banned}))
+        if any(t < 0 for t in banned):
+            raise ValueError("banned token ids must be >= 0")
+        for name, v in (("repetition", repetition), ("presence", presence), ("frequency", frequency), ("min_p", min_p),
+                        ("logit_bias", logit_bias), ("banned", banned)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Penalties is immutable")
+
+    def __repr__(self):
+        return (f"Penalties(repetition={self.repetition}, presence={self.presence}, frequency={self.frequency}, "
+                f"min_p={self.min_p}, logit_bias={'None' if self.logit_bias is None else '...'}, banned={self.banned})")
+
+    def bias_row(self, V: int, device) -> Optional[torch.Tensor]:
+        """The fp32 (V,) bias row of a call -- ``logit_bias`` with ``-inf`` at the banned tokens -- or None."""
+        if self.logit_bias is None and not self.banned:
+            return None
+        row = torch.zeros(V, dtype=torch.float32)
+        if isinstance(self.logit_bias, torch.Tensor):
+            if self.logit_bias.shape[0] != V:
+                raise ValueError(f"the logit_bias tensor has {self.logit_bias.shape[0]} entries, the vocabulary {V}")
+            row = self.logit_bias.to("cpu", torch.float32).clone()
+        ids = list(self.logit_bias) if isinstance(self.logit_bias, dict) else []
+        if any(t >= V for t in ids + list(self.banned)):
+            raise ValueError(f"a logit_bias or banned token id is outside the vocabulary of {V}")
+        for t in ids:
+            row[t] = self.logit_bias[t]
+        if self.banned:
+            row[list(self.banned)] = float("-inf")
+        if bool((row == float("-inf")).all()):
+            raise ValueError("logit_bias and banned leave no token")
+        return row.to(device)
+
+    def floor_gap(self, temperature: float) -> Optional[float]:
+        """``T * ln(min_p)`` in double, rounded to fp32; None where min-p is off."""
+        if self.min_p <= 0 or not temperature > 0:
+            return None
+        return torch.tensor(temperature * math.log(self.min_p), dtype=torch.float64).to(torch.float32).item()
+
+
+class _PenaltyState:
+    """What a generate loop holds on the device to penalise its rows: the int32 token histories (B, cap),
+    their lengths, the prompt lengths and the call's bias row.  ``apply`` is the loop's one
+    ``ops.penalize_rows`` launch; ``append`` adds a step's tokens with no host sync."""
+
+    def __init__(self, penalties: Penalties, sampler: "Sampler", V: int, device, hist, hlen, gen_start):
+        self.pen, self.hist, self.hlen, self.gen_start = penalties, hist, hlen, gen_start
+        self.bias = penalties.bias_row(V, device)
+        self.gap = penalties.floor_gap(sampler.temperature)
+
+    @classmethod
+    def from_prompts(cls, penalties, sampler, V: int, device, prompts, max_new_tokens: int):
+        lens = [int(p.shape[0]) for p in prompts]
+        hist = torch.zeros(len(prompts), max(lens) + max_new_tokens, dtype=torch.int32, device=device)
+        hist[:, :max(lens)] = torch.nn.utils.rnn.pad_sequence(list(prompts), batch_first=True).to(device, torch.int32)
+        lens = torch.tensor(lens, dtype=torch.int32, device=device)
+        return cls(penalties, sampler, V, device, hist, lens.clone(), lens)
+
+    def apply(self, logits, draft=None, dcnt=None, rows_per_seq: int = 1):
+        p = self.pen
+        return ops.penalize_rows(logits, self.hist, self.hlen, self.gen_start, draft, dcnt, p.repetition, p.presence,
+                                 p.frequency, self.gap, self.bias, rows_per_seq)
+
+    def append(self, tok) -> None:
+        self.hist.scatter_(1, self.hlen.long()[:, None], tok.to(torch.int32))
+        self.hlen += 1
+
+
+def _check_penalties(penalties, sampler) -> None:
+    if not isinstance(penalties, Penalties):
+        raise ValueError("penalties must be a Penalties")
+    if sampler is None:
+        raise ValueError("penalties need a sampler: they are applied in front of ops.sample_rows, not of the "
+                         "reference's softmax + torch.multinomial")
 
 
 class Speculation:
@@ -613,14 +724,25 @@ def prefill_logits(model, idx: torch.Tensor, cache: KVCache, prefill_chunk=None)
 
 @torch.no_grad()
 def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk=None,
-                    sampler: Optional[Sampler] = None) -> torch.Tensor:
+                    sampler: Optional[Sampler] = None, penalties: Optional[Penalties] = None) -> torch.Tensor:
     check_prefill_chunk(prefill_chunk)
+    if penalties is not None:
+        _check_penalties(penalties, sampler)
     cache = KVCache()
+    state = None
     for step in range(max_new_tokens):
         if prefill_chunk is not None and (cache.length == 0 or idx.shape[1] != cache.length + 1):
             logits = prefill_logits(model, idx, cache, prefill_chunk)
         else:
             logits = last_logits(model, idx, cache)
+        if penalties is not None:
+            if state is None:
+                state = _PenaltyState.from_prompts(penalties, sampler, logits.shape[-1], logits.device, list(idx),
+                                                   max_new_tokens)
+            tok = sampler.sample(state.apply(logits), step)
+            state.append(tok)
+            idx = torch.cat((idx, tok), dim=1)
+            continue
         if sampler is not None:
             idx = torch.cat((idx, sampler.sample(logits, step)), dim=1)
             continue
@@ -630,11 +752,25 @@ def cached_generate(model, idx: torch.Tensor, max_new_tokens: int, prefill_chunk
 
 
 @torch.no_grad()
-def naive_generate(model, idx: torch.Tensor, max_new_tokens: int, sampler: Sampler) -> torch.Tensor:
-    """The models' full-recompute ``generate`` loop with a ``Sampler`` in place of softmax + multinomial."""
+def naive_generate(model, idx: torch.Tensor, max_new_tokens: int, sampler: Sampler,
+                   penalties: Optional[Penalties] = None) -> torch.Tensor:
+    """The models' full-recompute ``generate`` loop with a ``Sampler`` in place of softmax + multinomial
+    (and, with ``penalties``, one ``ops.penalize_rows`` launch in front of it)."""
+    state = None
+    if penalties is not None:
+        _check_penalties(penalties, sampler)
     for step in range(max_new_tokens):
         logits, _ = model(idx[:, -model.block_size:])
-        idx = torch.cat((idx, sampler.sample(logits[:, -1, :], step)), dim=1)
+        logits = logits[:, -1, :]
+        if penalties is not None:
+            if state is None:
+                state = _PenaltyState.from_prompts(penalties, sampler, logits.shape[-1], logits.device, list(idx),
+                                                   max_new_tokens)
+            logits = state.apply(logits)
+        tok = sampler.sample(logits, step)
+        if state is not None:
+            state.append(tok)
+        idx = torch.cat((idx, tok), dim=1)
     return idx
 
 
@@ -904,18 +1040,23 @@ def _append_parts(step, lens, have: Sequence[int], cnt: Sequence[int], new_idx, 
 
 
 def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode, sampler: Optional[Sampler] = None,
-                   streams: Optional[torch.Tensor] = None):
+                   streams: Optional[torch.Tensor] = None, penalties: Optional["_PenaltyState"] = None):
     """The reference's sampling loop (softmax of the last logits, one ``torch.multinomial``
     over the whole batch; with a ``sampler``, one ``ops.sample_rows`` launch that draws row b's
     ``step``-th token from (seed, ``streams[b]`` or b, step)) for ``max_new_tokens >= 1`` tokens; ``decode(tok, active)`` is the
     cache's one-token step, ``active`` the device mask of the sequences that have not
     sampled ``eos_id`` (None without one).  Returns (toks (B, max_new_tokens), keep): sequence
-    b keeps its first keep[b] tokens, up to its first ``eos_id`` -- the loop's one host sync."""
+    b keeps its first keep[b] tokens, up to its first ``eos_id`` -- the loop's one host sync.
+    ``penalties``: the loop's ``_PenaltyState`` (one history row per row of ``logits``); every step then runs
+    ``ops.penalize_rows`` in front of the sampler and appends its tokens to the histories on the device."""
     B = logits.shape[0]
     active = None if eos_id is None else torch.ones(B, dtype=torch.bool, device=logits.device)
     new = []
     for step in range(max_new_tokens):
-        if sampler is not None:
+        if penalties is not None:
+            tok = sampler.sample(penalties.apply(logits), step, streams)
+            penalties.append(tok)
+        elif sampler is not None:
             tok = sampler.sample(logits, step, streams)
         else:
             probs = F.softmax(logits, dim=-1)
@@ -935,9 +1076,12 @@ def _sample_tokens(logits, max_new_tokens: int, eos_id: Optional[int], decode, s
     return toks, keep
 
 
-def _check_speculate(speculate, sampler, n_samples: int = 1, shared_decode: bool = False) -> None:
+def _check_speculate(speculate, sampler, n_samples: int = 1, shared_decode: bool = False, penalties=None) -> None:
     if not isinstance(speculate, Speculation):
         raise ValueError("speculate must be a Speculation")
+    if penalties is not None and speculate.graph:
+        raise ValueError("Speculation(graph=True) with penalties is not supported: the captured round does not "
+                         "hold the ops.penalize_rows launch")
     if sampler is None:
         raise ValueError("speculate needs a sampler: the reference's batch-wide torch.multinomial has no "
                          "per-sequence stream to couple the verification to")
@@ -949,7 +1093,7 @@ def _check_speculate(speculate, sampler, n_samples: int = 1, shared_decode: bool
 
 def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[int], sampler: Sampler,
                         streams: Optional[torch.Tensor], spec: Speculation, bs: int, append, truncate,
-                        fixed=None):
+                        fixed=None, penalties: Optional[Penalties] = None):
     """``_sample_tokens`` by speculative rounds, for ``max_new_tokens >= 1``.  ``logits`` (B, vocab) are the
     prefill's; ``append(new_idx, counts)`` is the cache's multi-row step with ``all_rows=True`` and
     ``truncate(lengths)`` its roll-back.  Per sequence the device holds the token history (prompt and
@@ -967,7 +1111,12 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
     same small tensor back and settles the host's copy of the lengths (``PagedKVCache._rolled_back``; the
     device lengths are already right).  A round in which a live sequence has ``length + K + 1 > block_size``
     -- its padded rows would not fit the window -- takes the eager path above on the same state; the two
-    give the same tokens, so they may interleave."""
+    give the same tokens, so they may interleave.
+
+    ``penalties``: the first token's logits and every round's rows pass through ``ops.penalize_rows`` with the
+    loop's own ``hist`` / ``hlen`` / ``draft`` / ``dcnt`` and the prompt lengths as ``gen_start``: row j is
+    penalised with the history plus the j drafts before it, what the plain loop sees there if they are accepted
+    (eager rounds only)."""
     dev = logits.device
     B, K = len(prompts), spec.k
     lens = [int(p.shape[0]) for p in prompts]
@@ -1008,6 +1157,11 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
         return host[0:2 * B:2], host[1:2 * B:2], host[2 * B:]
 
     have = list(lens)                                            # rows in the cache
+    pen = None
+    if penalties is not None:
+        pen = _PenaltyState(penalties, sampler, logits.shape[-1], dev, hist, hlen,
+                            torch.tensor(lens, dtype=torch.int32, device=dev))
+        logits = pen.apply(logits)
     tok = sampler.sample(logits, 0, strm)                        # (B, 1): offset 0 of every stream
     m, dc, rem = accept(tok)
     stats["emitted"] += sum(m)
@@ -1042,6 +1196,8 @@ def _speculative_tokens(logits, prompts, max_new_tokens: int, eos_id: Optional[i
         drafted = torch.where(cols[None, :Tn - 1] < dcnt[:, None], draft[:, :Tn - 1], 0)
         new_idx = torch.cat([pending, drafted], dim=1).long().clamp_(min=0)
         rows = append(new_idx, counts)                           # (B, Tn, vocab)
+        if pen is not None:
+            rows = pen.apply(rows.reshape(B * Tn, -1), draft, dcnt, Tn).view(B, Tn, -1)
         offset = (max_new_tokens - remaining.long())[:, None] + torch.arange(Tn, device=dev)[None, :]
         tok = ops.sample_rows(rows, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed,
                               strm[:, None].expand(B, Tn).reshape(-1), offset.reshape(-1))
@@ -1146,7 +1302,8 @@ def append_ragged(model, new_idx: torch.Tensor, counts, cache: RaggedKVCache, al
 @torch.no_grad()
 def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, eos_id: Optional[int] = None,
                     graph: bool = False, fused_step: bool = False, sampler: Optional[Sampler] = None,
-                    streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None):
+                    streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None,
+                    penalties: Optional[Penalties] = None):
     """``generate`` for B prompts of different lengths as one batch (any of the three
     models): one ``prefill_ragged``, then one ``decode_ragged`` step per token.  Sampling
     is the reference's (softmax of the last logits, ``torch.multinomial`` over the whole
@@ -1171,10 +1328,16 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
     has a plan reads the cache once and every row is the one-row decode's; ``graph`` / ``fused_step`` keep
     their meaning for one-token steps and rounds do not use the graph; a round reads three small integers
     per sequence back.  ``Speculation(graph=True)`` replays each round as one captured HIP graph of K + 1 rows
-    per sequence (``SpecRound``); the cache then keeps the storage of ``lengths`` as with ``graph=True``."""
+    per sequence (``SpecRound``); the cache then keeps the storage of ``lengths`` as with ``graph=True``.
+    ``penalties``: a ``Penalties`` (needs a ``sampler``) puts one ``ops.penalize_rows`` launch in front of every
+    ``ops.sample_rows`` one, eagerly after the step or its replay; the loop keeps the token histories on the
+    device and appends to them without a host sync.  With ``speculate`` the tokens stay the plain loop's (not
+    with ``Speculation(graph=True)``: ``ValueError``).  None (the default): the loops as they were."""
     bs = model.block_size
+    if penalties is not None:
+        _check_penalties(penalties, sampler)
     if speculate is not None:
-        _check_speculate(speculate, sampler)
+        _check_speculate(speculate, sampler, penalties=penalties)
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
@@ -1188,11 +1351,13 @@ def generate_ragged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int,
         outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
                                    _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
                                    lambda idx, counts: append_ragged(model, idx, counts, cache, all_rows=True),
-                                   cache.truncate, (model, cache, None))
+                                   cache.truncate, (model, cache, None), penalties)
         return [o.to(p.device) for o, p in zip(outs, prompts)]
+    state = None if penalties is None else _PenaltyState.from_prompts(penalties, sampler, logits.shape[-1],
+                                                                      logits.device, prompts, max_new_tokens)
     toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
                                 lambda tok, active: decode_ragged(model, tok, cache, active), sampler,
-                                _stream_ids(streams, len(prompts), 1, logits.device))
+                                _stream_ids(streams, len(prompts), 1, logits.device), state)
     return [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(prompts)]
 
 
@@ -1716,7 +1881,8 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
                    n_samples: int = 1, num_pages: Optional[int] = None, page_size: int = 64, kv_dtype=None,
                    rows_decode: bool = False, shared_decode: bool = False, graph: bool = False,
                    fused_step: bool = False, sampler: Optional[Sampler] = None,
-                   streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None):
+                   streams: Optional[Sequence[int]] = None, speculate: Optional[Speculation] = None,
+                   penalties: Optional[Penalties] = None):
     """``generate_ragged`` on a ``PagedKVCache``: same prefill, same reference sampling
     (softmax of the last logits, one ``torch.multinomial`` over the whole batch), one
     window (``ValueError`` if a prompt plus ``max_new_tokens`` crosses ``block_size``), the
@@ -1738,12 +1904,16 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
     ``speculate``: ``generate_ragged``'s (not with ``n_samples > 1`` or ``shared_decode``); the pool is made
     with ``rows_decode=True``, a round takes pages for its drafted rows and ``truncate`` returns those of
     the rejected ones, so the default ``num_pages`` still holds the call; with ``Speculation(graph=True)`` the
-    pages are taken before the round's replay and returned after the read of its result."""
+    pages are taken before the round's replay and returned after the read of its result.
+    ``penalties``: ``generate_ragged``'s; with ``n_samples > 1`` every sample has its own history row and its
+    prompt's length as ``gen_start``, so each equals its own one-sample run."""
     bs = model.block_size
     if n_samples < 1:
         raise ValueError("n_samples must be >= 1")
+    if penalties is not None:
+        _check_penalties(penalties, sampler)
     if speculate is not None:
-        _check_speculate(speculate, sampler, n_samples, shared_decode)
+        _check_speculate(speculate, sampler, n_samples, shared_decode, penalties)
     for p in prompts:
         if p.shape[0] + max_new_tokens > bs:
             raise ValueError(f"a prompt of {p.shape[0]} tokens plus {max_new_tokens} new ones crosses "
@@ -1768,16 +1938,18 @@ def generate_paged(model, prompts: Sequence[torch.Tensor], max_new_tokens: int, 
         outs = _speculative_tokens(logits, prompts, max_new_tokens, eos_id, sampler,
                                    _stream_ids(streams, len(prompts), 1, logits.device), speculate, bs,
                                    lambda idx, counts: append_paged(model, roots, idx, counts, cache, all_rows=True),
-                                   roll_back, (model, cache, roots))
+                                   roll_back, (model, cache, roots), penalties)
         return [o.to(p.device) for o, p in zip(outs, prompts)]
     seqs = [q for root in roots for q in [root] + [cache.fork(root) for _ in range(n_samples - 1)]]
     outs = [p for p in prompts for _ in range(n_samples)]
     if max_new_tokens >= 1:
         if n_samples > 1:
             logits = logits.repeat_interleave(n_samples, dim=0)
+        state = None if penalties is None else _PenaltyState.from_prompts(penalties, sampler, logits.shape[-1],
+                                                                          logits.device, outs, max_new_tokens)
         toks, keep = _sample_tokens(logits, max_new_tokens, eos_id,
                                     lambda tok, active: decode_paged(model, seqs, tok, cache, active), sampler,
-                                    _stream_ids(streams, len(prompts), n_samples, logits.device))
+                                    _stream_ids(streams, len(prompts), n_samples, logits.device), state)
         outs = [torch.cat([p, toks[b, :keep[b]].to(p.device)]) for b, p in enumerate(outs)]
     else:
         outs = [p.clone() for p in outs]

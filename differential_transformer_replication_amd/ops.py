@@ -1529,6 +1529,187 @@ def sample_rows(logits: Tensor, temperature=1.0, top_k=0, top_p=1.0, seed: int =
     return (tokens, logprobs.reshape(logits.shape[:-1])) if return_logprobs else tokens
 
 
+# ------------------------------------------------------- sampling penalties ---
+# Repetition / frequency / presence penalties, a logit bias and the min-p floor of logits rows, written as
+# fp32 rows for ``sample_rows``.  A row is penalised with its sequence's token history plus the drafted
+# tokens that precede it in a speculative round, so a round's rows see what the plain loop would have seen.
+# The definition is include/diffattn.h's ("Sampling penalties"); ``penalize_rows`` is the HIP kernel,
+# ``penalize_rows_reference`` the same definition in torch.
+PENALTY_LDS_MAX_V = 40944          # DTA_PENALTY_LDS_MAX_V: up to here the count table is in LDS, no workspace
+_PENALTY_WS: Dict[Tuple[torch.device, int], Tensor] = {}
+
+
+def penalize_rows_supported() -> bool:
+    """Whether the loaded library has ``dta_penalize_rows`` (an older build of the same ABI may not)."""
+    return _lib.penalty_symbols(_lib.load())
+
+
+def _penalty_param(v, B: int, device, name: str):
+    """A penalty parameter as (scalar, per-sequence fp32 tensor or None)."""
+    if isinstance(v, Tensor):
+        if v.numel() != B or v.device != device:
+            raise ValueError(f"{name} must be a scalar or a tensor of {B} entries on {device}")
+        return None, v.reshape(B).to(torch.float32).contiguous()
+    v = float(v)
+    if v != v:
+        raise ValueError(f"{name} is NaN")
+    return v, None
+
+
+def _penalty_check(logits, hist, hlen, gen_start, draft, dcnt, repetition, presence, frequency, floor_gap, bias,
+                   rows_per_seq, out):
+    """The shapes and values both implementations insist on; returns (x2, B, Tn, K, the four parameters as
+    (scalar, tensor) pairs, bias as (B or 1, V) or None)."""
+    x2 = _sample_rows_2d(logits)
+    R, V = x2.shape
+    dev = x2.device
+    Tn = int(rows_per_seq)
+    if hist.dim() != 2 or hist.shape[1] < 1 or Tn < 1:
+        raise ValueError("hist must be (B, cap) with cap >= 1, and rows_per_seq >= 1")
+    B, cap = hist.shape
+    if R != B * Tn:
+        raise ValueError(f"logits has {R} rows, hist {B} sequences of rows_per_seq {Tn} rows each")
+    if cap > 1 << 30:
+        raise ValueError(f"cap {cap} is above 2^30")
+    if (draft is None) != (dcnt is None):
+        raise ValueError("draft and dcnt come together")
+    K = 0
+    ints = [("hist", hist, (B, cap)), ("hlen", hlen, (B,))]
+    if gen_start is not None:
+        ints.append(("gen_start", gen_start, (B,)))
+    if draft is not None:
+        if draft.dim() != 2 or draft.shape[1] > SPEC_MAX_K:
+            raise ValueError(f"draft must be (B, K) with K <= {SPEC_MAX_K}")
+        K = draft.shape[1]
+        ints += [("draft", draft, (B, K)), ("dcnt", dcnt, (B,))]
+    for name, t, shape in ints:
+        if not isinstance(t, Tensor) or t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{name} must be an int32 {shape} tensor on {dev}")
+        if t.dim() == 1 and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.dim() == 2 and ((t.stride(1) != 1 and t.shape[1] > 1) or (B > 1 and t.stride(0) < t.shape[1])):
+            raise ValueError(f"{name} must have contiguous rows")
+    theta = _penalty_param(repetition, B, dev, "repetition")
+    if theta[0] is not None and theta[0] <= 0:
+        raise ValueError(f"repetition {theta[0]} must be positive")
+    pres = _penalty_param(presence, B, dev, "presence")
+    freq = _penalty_param(frequency, B, dev, "frequency")
+    gap = _penalty_param(0.0 if floor_gap is None else floor_gap, B, dev, "floor_gap")
+    if bias is not None:
+        if not isinstance(bias, Tensor) or bias.dtype != torch.float32 or bias.device != dev or \
+                tuple(bias.shape) not in ((V,), (1, V), (B, V)) or (V > 1 and bias.stride(-1) != 1):
+            raise ValueError(f"bias must be an fp32 ({V},) or ({B}, {V}) tensor on {dev} with contiguous rows")
+        bias = bias.reshape(-1, V)
+    if out is not None:
+        if not isinstance(out, Tensor) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (R, V) \
+                or (V > 1 and out.stride(1) != 1) or (R > 1 and out.stride(0) < V):
+            raise ValueError(f"out must be an fp32 ({R}, {V}) tensor on {dev} with contiguous rows that do not overlap")
+    return x2, B, Tn, K, theta, pres, freq, gap, bias
+
+
+def penalize_rows_reference(logits: Tensor, hist: Tensor, hlen: Tensor, gen_start: Optional[Tensor] = None,
+                            draft: Optional[Tensor] = None, dcnt: Optional[Tensor] = None, repetition=1.0,
+                            presence=0.0, frequency=0.0, floor_gap=None, bias: Optional[Tensor] = None,
+                            rows_per_seq: int = 1, out: Optional[Tensor] = None) -> Tensor:
+    """``penalize_rows`` in torch fp32 elementwise ops, on the tensors' device: include/diffattn.h's definition,
+    one rounding per operation.  Run on CPU tensors it equals the kernel bit for bit (the GPU tests hold the
+    kernel to that run; the payload of a NaN that the arithmetic itself makes, inf - inf, is the one thing left
+    open); run on the GPU it is torch's device arithmetic, which has not been held to the kernel's last bit.
+    The tests' oracle, and what ``penalize_rows`` runs on CPU tensors and on a library without
+    ``dta_penalize_rows``."""
+    x2, B, Tn, K, theta, pres, freq, gap, bias = _penalty_check(logits, hist, hlen, gen_start, draft, dcnt, repetition,
+                                                                presence, frequency, floor_gap, bias, rows_per_seq, out)
+    R, V = x2.shape
+    dev = x2.device
+    cap = hist.shape[1]
+    rows = lambda sv: (sv[1] if sv[1] is not None else torch.full((B,), sv[0], dtype=torch.float32, device=dev)
+                       ).repeat_interleave(Tn)[:, None]                                   # noqa: E731
+    theta, pres, freq, gap = rows(theta), rows(pres), rows(freq), rows(gap)
+    # the context: counts of the history from gen_start on, the seen flag of all of it, the draft prefix per row
+    L = hlen.long().clamp(0, cap)
+    g = (gen_start.long() if gen_start is not None else torch.zeros_like(L)).clamp(min=0).minimum(L)
+    t = torch.arange(cap, device=dev)[None, :]
+    h = hist.long()
+    ok = (t < L[:, None]) & (h >= 0) & (h < V)
+    col = torch.where(ok, h, V)                                                           # column V: ignored
+    seen = torch.zeros(B, V + 1, dtype=torch.int64, device=dev).scatter_add_(1, col, ok.long())
+    cnt = torch.zeros(B, V + 1, dtype=torch.int64, device=dev).scatter_add_(1, col, (ok & (t >= g[:, None])).long())
+    seen, cnt = seen.repeat_interleave(Tn, dim=0), cnt.repeat_interleave(Tn, dim=0)
+    if draft is not None and K > 0:
+        j = torch.arange(Tn, device=dev).repeat(B)
+        e = torch.minimum(j, dcnt.long().clamp(0, K).repeat_interleave(Tn))
+        dr = draft.long().repeat_interleave(Tn, dim=0)
+        ok = (torch.arange(K, device=dev)[None, :] < e[:, None]) & (dr >= 0) & (dr < V)
+        add = torch.zeros(R, V + 1, dtype=torch.int64, device=dev).scatter_add_(1, torch.where(ok, dr, V), ok.long())
+        seen, cnt = seen + add, cnt + add
+    seen, cnt = seen[:, :V] > 0, cnt[:, :V]
+    x0 = x2.float()
+    nan = torch.isnan(x0)
+    ninf = torch.full_like(x0, float("-inf"))
+    x = x0
+    on = ~torch.isnan(theta) & (theta != 1)
+    x = torch.where(seen & on, torch.where(x > 0, x / theta, x * theta), x)
+    on = ~torch.isnan(freq) & ~torch.isnan(pres)
+    x = torch.where((cnt > 0) & on, (x - freq * cnt.float()) - pres, x)
+    if bias is not None:
+        x = x + (bias if bias.shape[0] == 1 else bias.repeat_interleave(Tn, dim=0))
+    m = torch.where(torch.isnan(x), ninf, x).max(dim=1, keepdim=True).values
+    on = torch.isfinite(gap) & (gap < 0) & torch.isfinite(m)
+    x = torch.where(on & ~torch.isnan(x) & ~(x >= m + gap), ninf, x)       # a NaN the arithmetic made stays one
+    x = torch.where(nan, x0, x)
+    if out is None:
+        return x.reshape(logits.shape)
+    out.copy_(x)
+    return out
+
+
+def penalize_rows(logits: Tensor, hist: Tensor, hlen: Tensor, gen_start: Optional[Tensor] = None,
+                  draft: Optional[Tensor] = None, dcnt: Optional[Tensor] = None, repetition=1.0, presence=0.0,
+                  frequency=0.0, floor_gap=None, bias: Optional[Tensor] = None, rows_per_seq: int = 1,
+                  out: Optional[Tensor] = None) -> Tensor:
+    """Penalised fp32 logits of B * ``rows_per_seq`` rows in one launch (``dta_penalize_rows``).  ``logits``
+    (B * rows_per_seq, V) -- or (..., V), flattened -- bf16, fp16 or fp32, any row stride; row ``j`` of sequence
+    ``b`` is penalised with ``hist[b, :hlen[b]]`` (int32 (B, cap) and (B,)) followed by the first
+    ``min(j, dcnt[b])`` tokens of ``draft[b]`` (int32 (B, K), K <= 7; optional).  ``gen_start`` int32 (B,): the
+    prompt lengths (None: 0) -- frequency and presence count from there on, repetition sees everything.
+    ``repetition`` (1: off; > 0), ``presence``, ``frequency``, ``floor_gap`` (``T * ln(min_p)`` as fp32; None or
+    ``>= 0``: off): each a scalar or a device tensor of B entries.  ``bias``: fp32 (V,) or (B, V), added after
+    the penalties; ``-inf`` bans a token.  A row's output is a bitwise function of the row, its sequence's state
+    and its parameters.  Returns fp32 shaped like ``logits`` (or ``out``, fp32 (R, V), rows of any stride).
+
+    ``V`` above ``PENALTY_LDS_MAX_V`` counts in a workspace kept per (device, size), so that a graph-captured
+    caller holds it by address; the buffers (4 R V bytes each) are kept for the life of the process, one per
+    distinct size -- eager speculative rounds of varying width make up to K + 1 of them.  CPU tensors, and a
+    library without the entry point, run ``penalize_rows_reference``."""
+    args = (logits, hist, hlen, gen_start, draft, dcnt, repetition, presence, frequency, floor_gap, bias, rows_per_seq, out)
+    if not isinstance(logits, Tensor) or logits.device.type != "cuda" or not penalize_rows_supported():
+        return penalize_rows_reference(*args)
+    x2, B, Tn, K, theta, pres, freq, gap, bias = _penalty_check(*args)
+    R, V = x2.shape
+    dev = x2.device
+    res = torch.empty(R, V, device=dev, dtype=torch.float32) if out is None else out
+    if R > 0:
+        lib = _lib.load()
+        need = lib.dta_penalize_rows_workspace_bytes(R, V)
+        ws = None
+        if need:
+            ws = _PENALTY_WS.get((dev, need))
+            if ws is None:
+                ws = _PENALTY_WS[(dev, need)] = torch.empty(need, device=dev, dtype=torch.uint8)
+        row = lambda t, n: t.stride(0) if t.shape[0] > 1 else n                           # noqa: E731
+        sc = lambda sv, default: default if sv[0] is None else sv[0]                      # noqa: E731
+        a = _lib.PenalizeRowsArgs(_lib.dtype_code(x2.dtype), B, Tn, V, hist.shape[1], K,
+                                  x2.data_ptr(), row(x2, V), res.data_ptr(), row(res, V),
+                                  hist.data_ptr(), row(hist, hist.shape[1]), hlen.data_ptr(), _lib.ptr(gen_start),
+                                  _lib.ptr(draft), row(draft, K) if draft is not None else 0, _lib.ptr(dcnt),
+                                  sc(theta, 1.0), sc(freq, 0.0), sc(pres, 0.0), sc(gap, 0.0),
+                                  _lib.ptr(theta[1]), _lib.ptr(freq[1]), _lib.ptr(pres[1]), _lib.ptr(gap[1]),
+                                  _lib.ptr(bias), 0 if bias is None or bias.shape[0] == 1 else bias.stride(0),
+                                  _lib.ptr(ws), need)
+        _lib.check(lib.dta_penalize_rows(a, _lib.stream_handle(dev)))
+    return res.reshape(logits.shape) if out is None else out
+
+
 # ------------------------------------------------------ speculative decoding ---
 # One round of prompt-lookup speculative decoding on the device: which of the round's sampled rows are
 # emitted, the append to the sequence's history and the next draft by n-gram lookup.  The definition is

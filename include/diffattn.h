@@ -75,6 +75,8 @@ extern "C" {
                                   scatter in one launch);
                                   still 9, added the same way: dta_sample_rows (seeded temperature /
                                   top-k / top-p sampling, one token per logits row);
+                                  still 9, added the same way: dta_penalize_rows (sampling penalties, logit
+                                  bias and min-p over logits rows), dta_penalize_rows_workspace_bytes;
                                8: lse_c workspace (the key-major kernel folds |c_i| into its probabilities);
                                7: per-stage backward branch-group caps (group_max_dq, group_max_dkdv);
                                6: obr_dtype (fp16 O_i for 16-bit activations);
@@ -856,6 +858,80 @@ typedef struct dta_sample_rows_args {
   float* logprob_out;                /* device [R], or NULL */
 } dta_sample_rows_args;
 int dta_sample_rows(const dta_sample_rows_args* a, void* stream);
+
+/* Sampling penalties: repetition / frequency / presence penalties, a logit bias (bans are a bias of -inf)
+ * and the min-p floor of logits rows, in one launch (one 256-thread workgroup per row; still ABI 9, the
+ * presence of the symbol is the capability check).  It writes fp32 rows that dta_sample_rows then samples.
+ * Rows: R = B * Tn; row r is row j = r % Tn of sequence b = r / Tn.  Per sequence the device holds what the
+ * speculative loop holds: hist[b][0 .. cap) and hlen_dev[b], optionally draft[b][0 .. K) and dcnt_dev[b],
+ * and gen_start_dev[b], the prompt's length (NULL: 0).
+ * Clamps, before anything is indexed:
+ *   L = clamp(hlen, 0, cap)   g = clamp(gen_start, 0, L)   d = clamp(dcnt, 0, K) (0 without a draft)
+ *   e = min(j, d)
+ * The row's context is hist[b][0 .. L) followed by draft[b][0 .. e): what the plain loop has seen at that
+ * position if the first j drafts are accepted (a row beyond an unaccepted draft is discarded anyway).  A
+ * context token outside [0, V) is ignored.  For column i:
+ *   s_i = 1 if i occurs anywhere in the context
+ *   c_i = the occurrences of i at history positions >= g, plus those in the draft prefix
+ * With x = float(logits[r][i]), theta = repetition, f = frequency, p = presence, gap = floor_gap (the
+ * per-sequence device value where the pointer is set, the scalar otherwise), in this order, every
+ * arithmetic operation one correctly rounded fp32 operation, nothing contracted:
+ *   1. repetition   off at theta == 1 (or a NaN device theta).  If s_i: x = (x > 0) ? x / theta : x * theta;
+ *                   the sign test is on the bits: -0 and +0 are not positive.
+ *   2. frequency /  off at a NaN device f or p.  If c_i > 0: x = (x - f * float(c_i)) - p.
+ *      presence
+ *   3. bias         if bias is given: x = x + bias[b][i] (bias_stride 0: one row bias[i] shared by all).
+ *   4. floor        min-p.  Off unless gap < 0 and finite.  m = the maximum over the row of the values
+ *                   after step 3 that are not NaN; x = (x >= m + gap) ? x : -inf.  The caller passes
+ *                   gap = fp32(T * ln(min_p)): the kernel sees neither T nor min_p.  A row whose m is
+ *                   not finite is left as step 3 made it.
+ * A NaN input is written through with its bits unchanged by every step.  (A NaN that the arithmetic
+ * itself makes, inf - inf, is a NaN in the output; its payload is not specified.)
+ * A row's output is a bitwise function of the row, its sequence's state and its parameters: independent of
+ * B, of the row's index, of alignment and of timing.  Nothing outside out[r][0 .. V) is written -- not
+ * the gap between rows where out_stride > V, and none of the inputs.
+ * Counting: a per-row table of V 32-bit entries (the count in the low 31 bits, "seen before g" in the top
+ * one), filled by integer atomics, which commute.  For V <= DTA_PENALTY_LDS_MAX_V (40944: 4 V bytes of
+ * the CU's 160 KiB of LDS next to the kernel's 16 static bytes) it lives in LDS and no workspace is
+ * needed; beyond, in `workspace`, dta_penalize_rows_workspace_bytes(R, V) = 4 R V bytes (0 on the LDS
+ * path), of whose contents nothing is assumed.  No floating-point atomics; 64-bit address arithmetic.
+ * Any V in [1, 2^20], any row strides (elements); vector accesses where a row starts aligned to them,
+ * element accesses otherwise.
+ * DTA_ERR_INVALID: B < 0, Tn < 0, B * Tn above 2^31 - 1, V < 1, an unknown dtype, cap outside 1 .. 2^30,
+ * K outside 0 .. 7, a row stride below its row (row_stride < V, out_stride < V, hist_stride < cap,
+ * draft_stride < K with a draft, bias_stride neither 0 nor >= V), a null logits / out / hist / hlen_dev
+ * with R > 0, draft without dcnt_dev or the reverse, a pointer not aligned to its element, a NaN scalar
+ * parameter, repetition <= 0, a workspace that is null or smaller than the query says where one is
+ * needed.  DTA_ERR_UNSUPPORTED: V > 2^20.  R == 0: DTA_OK, no launch. */
+#define DTA_PENALTY_LDS_MAX_V 40944
+typedef struct dta_penalize_rows_args {
+  int32_t dtype;
+  int32_t B, Tn, V;
+  int32_t cap;                       /* tokens a row of hist holds */
+  int32_t K;                         /* tokens a row of draft holds, 0 .. 7 */
+  const void* logits;                /* device [B * Tn][V], dtype */
+  int64_t row_stride;                /* elements */
+  float* out;                        /* device fp32 [B * Tn][V] */
+  int64_t out_stride;
+  const int32_t* hist;               /* device int32 [B][cap] */
+  int64_t hist_stride;
+  const int32_t* hlen_dev;           /* device int32 [B] */
+  const int32_t* gen_start_dev;      /* device int32 [B], or NULL: 0 */
+  const int32_t* draft;              /* device int32 [B][K], or NULL */
+  int64_t draft_stride;
+  const int32_t* dcnt_dev;           /* device int32 [B]; with draft */
+  float repetition, frequency, presence, floor_gap;   /* used where the per-sequence pointer is NULL */
+  const float* repetition_dev;       /* device fp32 [B], or NULL */
+  const float* frequency_dev;
+  const float* presence_dev;
+  const float* floor_gap_dev;
+  const float* bias;                 /* device fp32 [B][V] or [V], or NULL */
+  int64_t bias_stride;               /* elements; 0: one shared row */
+  void* workspace;                   /* device, dta_penalize_rows_workspace_bytes(B * Tn, V) bytes; may be NULL at 0 */
+  size_t workspace_bytes;
+} dta_penalize_rows_args;
+size_t dta_penalize_rows_workspace_bytes(int64_t R, int32_t V);
+int dta_penalize_rows(const dta_penalize_rows_args* a, void* stream);
 
 /* Speculative decoding: one round's acceptance and the next prompt-lookup draft in one launch (still
  * ABI 9; the presence of the symbol is the capability check).  One 256-thread workgroup per sequence.
